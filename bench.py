@@ -18,7 +18,12 @@ Multi-GPU: reads shard across ranks with no data-path collective; the only colle
 per-sample count all-reduce over RCCL.  `--scaling weak` (default): every rank owns a full batch;
 `--scaling strong`: the config's N reads are split over the ranks (BASELINE config 3's wording).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--reads R]
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the roofline of the timed launches.
+`--full` adds everything else named above and below -- the parity gate against the oracle, `scopes`, the CPU rows, the strong-scaling
+pass of several ranks -- and the side file with the whole record.  `--dump-outputs DIR` writes what the last timed step left its
+caller (dump_outputs) so that two builds can be compared output for output: the inputs depend on the arguments alone.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--reads R] [--full] [--dump-outputs DIR]
         --gpus N > 1 without a torchrun environment re-launches itself as N ranks:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
@@ -184,6 +189,31 @@ def kernel_sources_digest() -> str:
     return h.hexdigest()
 
 
+DUMP_READS = 2_000_000   # three float32 arrays of this many reads: 24 MB
+DUMP_SEED = 20240229
+
+
+def dump_sample(n: int) -> np.ndarray:
+    """The read numbers (ascending, int64) whose results --dump-outputs writes from a batch of n > DUMP_READS reads."""
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_READS, dtype=np.int64))
+
+
+def dump_outputs(out_dir: str, d_out, d_counts) -> None:
+    """--dump-outputs: what a caller of fqtk_matcher_assign_batch_device holds after the last timed step, as .npy files.
+    idx / best / next (float32): the three fields of the per-read results, of every read of rank 0's batch up to DUMP_READS reads,
+    of a fixed seeded sample of DUMP_READS reads (ascending read numbers, the same for the same batch size) above that.
+    counts (float64): the per-sample count vector, unmatched last, as the K timed steps accumulated it (K x one step's counts)."""
+    import torch
+    n = d_out.numel()
+    if n > DUMP_READS:
+        d_out = d_out[torch.from_numpy(dump_sample(n)).to(d_out.device)]
+    got = d_out.cpu().numpy().view(DT)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("idx", "best", "next"):
+        np.save(os.path.join(out_dir, name + ".npy"), got[name].astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), d_counts.cpu().numpy().astype(np.float64))
+
+
 def self_launch(n_gpus: int) -> int:
     """--gpus N without a torchrun environment: start N ranks (one process per GPU) and relay the result."""
     import torch
@@ -227,7 +257,15 @@ def main() -> int:
                     help="use_cache=false: exhaustive per-sample scan for every read (no memo table)")
     ap.add_argument("--memo-table", action="store_true",
                     help="pin the HBM/L2 table form of the memo (default: LDS-resident form when it can be built)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity gate against the oracle, scopes B and E, the kernel rows, the CPU rows and "
+                         "(several ranks) the strong-scaling pass, and write the whole record to the side file the line names; without it "
+                         "--parity, --cpu-seconds and the --e2e-* options have nothing to act on")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left its caller as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the K steps, print the line
+        args.no_verify, args.no_scopes, args.cpu_seconds = True, True, 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
@@ -336,12 +374,14 @@ def main() -> int:
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events around the K launches, per launch
     matcher.poll_error(stream)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, d_counts)
 
     # ---- several ranks: the same K steps once more over 1 / world of the batch -- what every rank does when the
     #      config's N reads are SPLIT over the ranks (BASELINE config 3's wording: 400 M reads over 1 -> 8 GPUs); the
     #      line's `value` stays the weak-scaling one (every rank a full batch) unless --scaling strong was asked for
     strong = None
-    if use_dist and args.scaling == "weak":
+    if use_dist and args.scaling == "weak" and args.full:
         ns = max(1, (args.reads or cfg.n_reads) // world)
         d_counts_s = torch.zeros_like(d_counts)
         dist.barrier()
@@ -565,7 +605,7 @@ def main() -> int:
         # that the JSON line is the LAST thing on stdout
         import ctypes
         ctypes.CDLL(None).fflush(None)
-        print(json.dumps(one_line(out)), flush=True)
+        print(json.dumps(one_line(out, side_file=args.full)), flush=True)
     return 0
 
 
@@ -614,15 +654,18 @@ def device_scopes(scope_bench, args, dev_list, workload, value_k, pool, host_cor
     return scopes
 
 
-def one_line(out: dict) -> dict:
+def one_line(out: dict, side_file: bool = True) -> dict:
     """The ONE JSON line, short enough for whoever keeps only the end of this program's output (the driver keeps 2000 characters):
     every field of the contract, the scopes as numbers.  The whole record -- what every scope ran, its stages and timelines, the
     CPU rows' samples -- goes to gpurun_out/bench_detail.json (profiles/ keeps copies of the runs quoted in DESIGN.md)."""
     detail = os.path.join(ROOT, "gpurun_out", "bench_detail.json")
     try:
-        os.makedirs(os.path.dirname(detail), exist_ok=True)
-        with open(detail, "w") as fh:
-            json.dump(out, fh, indent=1)
+        if side_file:
+            os.makedirs(os.path.dirname(detail), exist_ok=True)
+            with open(detail, "w") as fh:
+                json.dump(out, fh, indent=1)
+        else:   # a plain run writes no file of its own
+            detail = None
     except OSError:
         detail = None
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "settle_steps", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -677,6 +720,10 @@ if __name__ == "__main__":
     profiled = any(k.startswith("ROCPROF") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
     if profiled or os.environ.get("FQTK_CLEAN_EXIT", "0") not in ("", "0"):
         sys.exit(rc)
+    # (what registered itself with atexit -- a tracer, a coverage or audit hook of whoever started this program -- still runs: only the
+    #  teardown after it is skipped)
+    import atexit
+    atexit._run_exitfuncs()
     sys.stdout.flush()
     sys.stderr.flush()
     os._exit(rc or 0)

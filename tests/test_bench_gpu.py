@@ -1,5 +1,5 @@
-"""bench.py on the GPU box: the scopes / CPU rows / parity gate of the JSON line, the RCCL code path with
-one rank, and the --gpus N self-launch (N real ranks when the box has them, a loud refusal when not)."""
+"""bench.py on the GPU box: the plain run and its --dump-outputs files, the scopes / CPU rows / parity gate of the --full line, the RCCL
+code path with one rank, and the --gpus N self-launch (N real ranks when the box has them, a loud refusal when not)."""
 import json
 import os
 import subprocess
@@ -24,7 +24,7 @@ def _line(r):
 
 @pytest.mark.gpu
 def test_bench_line_carries_scopes_create_time_cpu_rows_and_the_full_parity_gate():
-    r = _run(["--reads", "3000000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--e2e-templates", "4000000", "--e2e-threads", "8"])
+    r = _run(["--full", "--reads", "3000000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--e2e-templates", "4000000", "--e2e-threads", "8"])
     line = r.stdout.strip().splitlines()[-1]
     d = _line(r)
     # the line fits the tail its consumer keeps, and carries every field of the contract and every scope as numbers
@@ -62,8 +62,39 @@ def test_bench_line_carries_scopes_create_time_cpu_rows_and_the_full_parity_gate
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_steps_only_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full: the line of the timed steps and nothing that takes runs of its own, no side file.  --dump-outputs: the results
+    of a fixed sample of the reads (2.5 M reads: more than one dump holds) and the count vector, all equal to the oracle's."""
+    import numpy as np
+    import bench
+    from fqtk_amd import synth
+    from oracle import oracle as O
+    n, steps = 2_500_000, 3
+    out = tmp_path / "dump"
+    d = _line(_run(["--gpus", "1", "--reads", str(n), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out)]))
+    assert d["steps"] == steps and d["unit"] == "M reads/s" and d["higher_is_better"] is True and d["dtype"] == "u8" and d["scope"] == "K"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / d["ms_per_step"] / 1e3) <= 0.01 * d["value"]
+    assert d["roofline"]["kernel_ms"] <= d["ms_per_step"] * 1.05
+    assert not {"scopes", "cpu_baseline", "detail", "strong_scaling"} & set(d) and d["config"]["parity"] == ""
+    cfg = synth.CONFIGS[3]
+    w = synth.Workload(cfg)
+    lit = O.RefLiteral(w.barcodes, cfg.max_mismatches, cfg.min_mismatch_delta, True)
+    i, b, nx, c = lit.assign_batch(np.ascontiguousarray(w.fill_host(0, n)[:, :cfg.barcode_len]))
+    pick = bench.dump_sample(n)
+    assert pick.shape == (bench.DUMP_READS,) and n > bench.DUMP_READS
+    size = 0
+    for name, want in (("idx", i[pick]), ("best", b[pick]), ("next", nx[pick])):
+        got = np.load(out / (name + ".npy"))
+        size += got.nbytes
+        assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32)), name
+    counts = np.load(out / "counts.npy")
+    assert counts.dtype == np.float64 and np.array_equal(counts, c.astype(np.float64) * steps)
+    assert size + counts.nbytes <= 64_000_000
+
+
+@pytest.mark.gpu
 def test_rccl_path_with_one_rank_allreduced_counts_match_the_oracle():
-    d = _line(_run(["--reads", "4000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-scopes",
+    d = _line(_run(["--full", "--reads", "4000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-scopes",
                     "--parity", "full"], env={"FQTK_BENCH_FORCE_DIST": "1"}))
     assert d["n_gpus"] == 1 and "count vector of all 4000000 reads" in d["config"]["parity"]
 
@@ -90,7 +121,7 @@ def test_gpus_n_launches_n_ranks_itself_or_refuses():
     have = torch.cuda.device_count()
     if have >= 2:
         for scaling in ("weak", "strong"):
-            d = _line(_run(["--gpus", "2", "--reads", "4000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
+            d = _line(_run(["--full", "--gpus", "2", "--reads", "4000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
                             "--scaling", scaling, "--parity", "full", "--e2e-templates", "4000000", "--e2e-threads", "8"]))
             assert d["n_gpus"] == 2 and d["scaling"] == scaling and len(d["roofline"]["kernel_ms_per_rank"]) == 2
             assert d["config"]["reads_per_step_whole_job"] == (8000000 if scaling == "weak" else 4000000)
@@ -105,7 +136,7 @@ def test_gpus_n_launches_n_ranks_itself_or_refuses():
 def test_scopes_b_and_e_over_several_devices_from_one_rank():
     """FQTK_BENCH_DEVICES=0,0: what rank 0 of an N > 1 job does for scopes B and E, on a one-GPU box (two matchers / two record
     pipelines on the same device)."""
-    d = _line(_run(["--reads", "3000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--e2e-templates", "4000000", "--e2e-threads", "8"],
+    d = _line(_run(["--full", "--reads", "3000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--e2e-templates", "4000000", "--e2e-threads", "8"],
                    env={"FQTK_BENCH_DEVICES": "0,0"}))
     assert d["n_gpus"] == 1 and d["scope"] == "K"
     _check_device_scopes(d, "0,0")

@@ -874,7 +874,7 @@ def _few_cpus():
 def test_full_size_parity_of_every_baseline_config():
     """The full-size gate: tools/full_parity.py over EVERY read of cfg 1-5 with the default memo path, plus the table
     form pinned on cfg 3 -- 0 mismatching (idx, best, next) triples and identical per-sample count vectors vs the
-    oracle.  (The default bench.py run checks the first 50 M triples + all 400 M counts of cfg 3 on its own.)"""
+    oracle.  (A bench.py --full run checks the first 50 M triples + all 400 M counts of cfg 3 on its own.)"""
     import json
     import os
     import subprocess

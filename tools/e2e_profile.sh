@@ -9,5 +9,5 @@ FQTK_ZLIB_INFLATE=1 python tools/scope_bench.py --skip-b --templates 16000000 --
 python tools/scope_bench.py --skip-b --templates 8000000 --repeat-block --threads 16 --bgzf >> $O/scope_E.jsonl 2>> $O/scope_E.err
 python tools/scope_bench.py --skip-b --templates 8000000 --repeat-block --threads 16 --bgzf --extra=--gpu-bgzf >> $O/scope_E.jsonl 2>> $O/scope_E.err
 python tools/soak_cli.py --iters 40 --seed 21 > $O/soak_cli.log 2>&1; tail -1 $O/soak_cli.log
-python bench.py > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-300
 tail -3 $O/pytest_gpu.log

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | cut -c1-200
 B="python $R/bench.py --cpu-seconds 0 --no-verify --no-scopes"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B > $O/stats.log 2>&1

@@ -14,7 +14,7 @@ if has bench; then
   cp gpurun_out/${TAG}_prof/bench.json $O/bench_line.json; cp gpurun_out/bench_detail.json $O/bench_detail_default.json 2>/dev/null
   cp gpurun_out/${TAG}_prof/stats/bench_kernel_stats.csv $O/bench_cfg3_kernel_stats.csv 2>/dev/null; cp gpurun_out/${TAG}_prof/pmc_traffic.json $O/pmc_traffic_cfg3.json 2>/dev/null
   cp gpurun_out/${TAG}_prof/pmc_traffic_for_bench.json $O/ 2>/dev/null
-  FQTK_BENCH_DEVICES=0,0 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_line_devices00.json 2> $O/bench_devices00.err; cp gpurun_out/bench_detail.json $O/bench_detail_devices00.json 2>/dev/null
+  FQTK_BENCH_DEVICES=0,0 python bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 > $O/bench_line_devices00.json 2> $O/bench_devices00.err; cp $O/../bench_detail.json $O/bench_detail_devices00.json 2>/dev/null
 fi
 if has matrix; then
   bash tools/bench_matrix.sh > $O/bench_matrix.jsonl 2> /dev/null
