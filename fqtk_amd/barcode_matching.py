@@ -124,6 +124,17 @@ class BarcodeMatcher:
     def memo_kind(self, kind: int) -> None:
         _check(self._lib.fqtk_matcher_set_memo_kind(self._h, int(kind)))
 
+    SCAN_VALU, SCAN_MFMA = 0, 1
+
+    @property
+    def scan_kind(self) -> int:
+        """Kernel of the exhaustive scan the next scanned batch runs: SCAN_VALU (one lane per read) or SCAN_MFMA (int8 matrix cores)."""
+        return int(self._lib.fqtk_matcher_scan_kind(self._h))
+
+    @scan_kind.setter
+    def scan_kind(self, kind: int) -> None:
+        _check(self._lib.fqtk_matcher_set_scan_kind(self._h, int(kind)))
+
     @property
     def memo_direct_bytes(self) -> int:
         """2 or 4 when MEMO_TABLE is the direct-indexed variant (barcodes of <= 10 bases), else 0."""

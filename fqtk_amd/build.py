@@ -26,6 +26,11 @@ TARGETS = {
 }
 
 
+# per-source flags.  fqtk_match.hip holds the MFMA scan: its translation unit is built with packed FP32 operations off (the matcher's
+# kernels are integer code and have none to lose; new kernels of this unit must not come to depend on v_pk_*_f32 forms)
+SOURCE_FLAGS = {"fqtk_match.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _stale(out: str, deps) -> bool:
     if not os.path.exists(out):
         return True
@@ -118,7 +123,8 @@ def build(force: bool = False, verbose: bool = False) -> None:
                 # (-fvisibility-inlines-hidden: the library's copies of inline C++ functions -- std::unique_lock::unlock ... -- are its own; a
                 #  C-ABI library neither exports them nor takes the executable's, which under TSan are instrumented while the lock they pair
                 #  with was taken in here, unseen: "unlock of an unlocked mutex")
-                jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden", "-I", INCLUDE, "-c", "-o", obj] + extra + extra_defs + [src])
+                jobs.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden", "-I", INCLUDE, "-c", "-o", obj] +
+                            extra + SOURCE_FLAGS.get(os.path.basename(src), []) + extra_defs + [src])
         links.append((os.path.join(LIBDIR, name), objs))
 
     def run(cmd):

@@ -36,6 +36,7 @@ extern "C" int fqtk_dev_phase_cycles(unsigned long long *out16) {
 #include "lds_memo_kernels.hip.h"
 #include "lds_memo_plan.hpp"
 #include "direct_memo_plan.hpp"
+#include "mfma_scan_kernels.hip.h"
 
 namespace {
 
@@ -184,6 +185,10 @@ struct fqtk_matcher {
     volatile uint32_t *h_seen = nullptr;     // page-locked: set by a memo kernel that met an IUPAC / junk byte in a read
     uint32_t *d_seen = nullptr;              // the same word, device address
     int use_cache = 1;                       // BarcodeMatcher.use_cache (barcode_matching.rs:41-42)
+    // the exhaustive scan on the matrix cores (mfma_scan_kernels.hip.h); rows absent when the table is not eligible
+    uint8_t *d_mfma_rows = nullptr;            // sample operand, [ntiles * 32][rs]
+    fqtk::MfmaScanPlan mfma{};
+    int scan_kind_wanted = -1;                 // -1 = auto, else FQTK_SCAN_VALU / FQTK_SCAN_MFMA (FQTK_SCAN, set_scan_kind)
     Slot slots[kNumSlots];
 };
 
@@ -240,6 +245,109 @@ int launch_vec(const fqtk::MatchParams &P, int num_cus, hipStream_t stream) {
         return launch_t<NW, R, -1>(P, num_cus, stream);
     }
     return launch_t<NW, R, 0>(P, num_cus, stream);
+}
+
+// Which exhaustive scan the next scanned batch runs.  Auto takes the MFMA scan only for shapes like those where the same-box
+// A/B of profiles/mfma_scan_ab.txt (tools/ab_scan.py) shows it ahead by more than the run-to-run
+// spread (about 1 %, 2.5 % at 96 x 16).  In G reads/s, VALU -> MFMA:
+//   ahead   96 x 4  43.4 -> 69.4    96 x 8  42.6 -> 49.3   128 x 8  33.0 -> 42.0   160 x 8  26.8 -> 36.4   128 x 12  32.3 -> 42.2
+//           384 x 8  11.5 -> 18.5   192 x 16  22.0 -> 27.1   384 x 16  11.4 -> 15.5   416 x 16  10.6 -> 11.8   512 x 16  8.7 -> 10.0
+//   level   96 x 16  41.0 -> 42.0 (inside the spread)   385 x 16  11.4 -> 11.8
+//   behind  97 x 8  42.3 -> 41.1 (a whole tile for one sample)   64 x 8  60.6 -> 58.6   24 x 8  125 -> 65.8   1536 x 10  2.88 -> 2.83
+//           4096 x 16  1.08 -> 0.72   384 x 17  11.4 -> 10.6   384 x 24  11.3 -> 10.7   384 x 32  11.1 -> 4.9   384 x 64  6.6 -> 2.1
+// So: at most 16 bases, whole tiles only (S a multiple of 32), at most 512 samples, and at least 96 (three K steps, L 13-16:
+// at least 192).  The shapes listed are the ones measured; the multiples of 32 between them and the other L <= 16 are taken
+// to behave like their neighbours and are NOT measured.
+int scan_kind_of(const fqtk_matcher *m) {
+    if (!m->d_mfma_rows) return FQTK_SCAN_VALU;
+    if (m->scan_kind_wanted >= 0) return m->scan_kind_wanted;
+    const bool ahead = m->L <= 16 && m->S % 32 == 0 && m->S <= 512 && m->S >= (m->L <= 12 ? 96u : 192u);
+    return ahead ? FQTK_SCAN_MFMA : FQTK_SCAN_VALU;
+}
+
+template <int NW, int KB, int RT, int VEC>
+int launch_mfma_t(const fqtk_matcher *m, const fqtk::MfmaScanParams &Q, hipStream_t stream) {
+    const fqtk::MfmaScanPlan &pl = m->mfma;
+    const uint64_t tile = (uint64_t)(pl.block / 64) * 32 * RT;
+    const uint64_t ntiles = (Q.m.n + tile - 1) / tile;
+    if (ntiles == 0) return FQTK_OK;
+    // persistent grid: as many workgroups as LDS and the variant's registers (mfma_block_cap threads per CU) let a CU hold
+    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(fqtk::kMfmaLdsBudget / pl.lds, fqtk::mfma_block_cap(KB) / pl.block));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->num_cus * per_cu);
+    auto kern = fqtk::mfma_scan_kernel<NW, KB, RT, VEC>;
+    const void *fn = reinterpret_cast<const void *>(kern);
+    if (pl.lds > 64 * 1024 && std::find(m->ldsm_big_lds_ok.begin(), m->ldsm_big_lds_ok.end(), fn) == m->ldsm_big_lds_ok.end()) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fqtk::kMfmaLdsBudget));
+        m->ldsm_big_lds_ok.push_back(fn);
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(pl.block), pl.lds, stream, Q);
+    HIP_TRY(hipGetLastError());
+    return FQTK_OK;
+}
+
+// The load paths of launch_vec; the packed vector loads exist for rows of at most 16 bytes (KB == 3).
+template <int NW, int KB, int RT>
+int launch_mfma_vec(const fqtk_matcher *m, const fqtk::MfmaScanParams &Q, hipStream_t stream) {
+    const fqtk::MatchParams &P = Q.m;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(P.obs);
+    const uint32_t nwords = (P.L + 3) / 4;
+    if (P.stride % 4 == 0 && base % 4 == 0 && P.stride >= nwords * 4) {
+        if constexpr (KB == 3) {
+            const uint32_t sw = P.stride / 4;
+            if (sw == nwords) {
+                if (sw == 4 && base % 16 == 0) return launch_mfma_t<NW, KB, RT, 4>(m, Q, stream);
+                if (sw == 2 && base % 8 == 0) return launch_mfma_t<NW, KB, RT, 2>(m, Q, stream);
+                if (sw == 1) return launch_mfma_t<NW, KB, RT, 1>(m, Q, stream);
+                if (sw == 3) return launch_mfma_t<NW, KB, RT, 3>(m, Q, stream);
+            }
+        }
+        return launch_mfma_t<NW, KB, RT, -1>(m, Q, stream);
+    }
+    return launch_mfma_t<NW, KB, RT, 0>(m, Q, stream);
+}
+
+int launch_mfma_scan(const fqtk_matcher *m, const fqtk::MatchParams &P, hipStream_t stream) {
+    const fqtk::MfmaScanPlan &pl = m->mfma;
+    fqtk::MfmaScanParams Q;
+    Q.m = P;
+    Q.rows = m->d_mfma_rows;
+    Q.lq = pl.lq;
+    Q.ks = pl.ks;
+    Q.rs = pl.rs;
+    Q.ntiles = pl.ntiles;
+    Q.chunk_tiles = pl.chunk_tiles;
+    if (pl.kb == 3) return launch_mfma_vec<1, 3, 2>(m, Q, stream);
+    if (pl.kb == 6) return launch_mfma_vec<1, 6, 2>(m, Q, stream);
+    switch (m->NW) {
+        case 2: return launch_mfma_vec<2, 0, 1>(m, Q, stream);
+        case 3: return launch_mfma_vec<3, 0, 1>(m, Q, stream);
+        case 4: return launch_mfma_vec<4, 0, 1>(m, Q, stream);
+        default: return fail(FQTK_EINVAL, "unsupported barcode length");
+    }
+}
+
+// The sample operand of the MFMA scan (layout: mfma_scan_kernels.hip.h), built once per matcher.  Not eligible
+// (more than kMfmaMaxSamples samples: the key has 14 index bits): no rows, the VALU scan serves.
+int build_mfma_rows(fqtk_matcher *m, const std::vector<std::vector<uint8_t>> &enc) {
+    m->mfma = fqtk::plan_mfma_scan(m->S, m->L, m->S + 1 <= fqtk::kMaxLdsHist);
+    if (!m->mfma.ok) return FQTK_OK;
+    const fqtk::MfmaScanPlan &pl = m->mfma;
+    std::vector<uint8_t> rows((size_t)pl.ntiles * 32 * pl.rs, 0);
+    for (uint32_t s = 0; s < m->S; ++s) {
+        uint8_t *row = rows.data() + (size_t)s * pl.rs;
+        for (uint32_t i = 0; i < m->L; ++i) {
+            const uint8_t e = enc[s][i];
+            for (uint32_t c = 0; c < 4; ++c)
+                if (!((e >> c) & 1u)) row[4 * i + c] = 0x80;
+            if (e != 15) row[4 * pl.lq + i] = 0x80;
+        }
+        row[5 * pl.lq] = (uint8_t)(s & 127u);
+        row[5 * pl.lq + 1] = (uint8_t)(0u - (s >> 7));
+    }
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_mfma_rows), rows.size()));
+    HIP_TRY(hipMemcpy(m->d_mfma_rows, rows.data(), rows.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return FQTK_OK;
 }
 
 template <int KW>
@@ -731,6 +839,7 @@ int launch_memo(const fqtk_matcher *m, const fqtk::MatchParams &P, hipStream_t s
             default: return launch_memo_vec<4>(m, Q, stream);
         }
     }
+    if (scan_kind_of(m) == FQTK_SCAN_MFMA) return launch_mfma_scan(m, P, stream);
     switch (m->NW) {
         case 1: return launch_vec<1, 4>(P, m->num_cus, stream);
         case 2: return launch_vec<2, 2>(P, m->num_cus, stream);
@@ -1398,6 +1507,14 @@ int fqtk_matcher_create(const char *const *barcodes, uint32_t n_samples, uint32_
         const int rc = build_memo(m, enc);
         if (rc != FQTK_OK) return cleanup(rc);
     }
+    {   // after the memo: its builder scans its candidates with match_kernel
+        const int rc = build_mfma_rows(m, enc);
+        if (rc != FQTK_OK) return cleanup(rc);
+    }
+    if (const char *sc = std::getenv("FQTK_SCAN")) {   // valu / mfma pin the scan (mfma: where the table is eligible); anything else is auto
+        if (!std::strcmp(sc, "valu")) m->scan_kind_wanted = FQTK_SCAN_VALU;
+        else if (!std::strcmp(sc, "mfma")) m->scan_kind_wanted = FQTK_SCAN_MFMA;
+    }
     *out = m;
     return FQTK_OK;
 }
@@ -1425,6 +1542,7 @@ void fqtk_matcher_destroy(fqtk_matcher *m) {
     if (m->d_direct) (void)hipFree(m->d_direct);
     if (m->d_hot2) (void)hipFree(m->d_hot2);
     if (m->d_ldsm) (void)hipFree(m->d_ldsm);
+    if (m->d_mfma_rows) (void)hipFree(m->d_mfma_rows);
     if (m->d_table) (void)hipFree(m->d_table);
     if (m->d_lut) (void)hipFree(m->d_lut);
     if (m->d_err) (void)hipFree(m->d_err);
@@ -1470,6 +1588,20 @@ int fqtk_matcher_set_memo_kind(fqtk_matcher *m, int kind) {
     if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
     if (kind != FQTK_MEMO_TABLE && kind != FQTK_MEMO_LDS) return fail(FQTK_EINVAL, "memo kind must be FQTK_MEMO_TABLE or FQTK_MEMO_LDS");
     m->memo_kind_wanted = kind == FQTK_MEMO_TABLE ? FQTK_MEMO_TABLE : 0;
+    return FQTK_OK;
+}
+
+int fqtk_matcher_scan_kind(const fqtk_matcher *m) { return m ? scan_kind_of(m) : FQTK_SCAN_VALU; }
+
+int fqtk_matcher_set_scan_kind(fqtk_matcher *m, int kind) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    if (kind != FQTK_SCAN_VALU && kind != FQTK_SCAN_MFMA) return fail(FQTK_EINVAL, "scan kind must be FQTK_SCAN_VALU or FQTK_SCAN_MFMA");
+    if (kind == FQTK_SCAN_MFMA && !m->d_mfma_rows) {
+        if (m->S > fqtk::kMfmaMaxSamples)
+            return fail(FQTK_EINVAL, "FQTK_SCAN_MFMA serves at most 16384 samples; this table has " + std::to_string(m->S));
+        return fail(FQTK_EINVAL, "FQTK_SCAN_MFMA: one tile of this table's rows does not fit LDS next to a workgroup's reads");
+    }
+    m->scan_kind_wanted = kind;
     return FQTK_OK;
 }
 

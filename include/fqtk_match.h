@@ -125,6 +125,20 @@ int fqtk_matcher_set_memo_kind(fqtk_matcher *m, int kind);
  * (2 or 4) when that variant is what FQTK_MEMO_TABLE means for this matcher, else 0. */
 int fqtk_matcher_memo_direct_bytes(const fqtk_matcher *m);
 
+/* Which kernel runs the exhaustive scan (tuning / test knob, no counterpart in the reference; results never depend on it).
+ * The scan serves every read when there is no memo (FQTK_MEMO_NONE: use_cache 0, barcode_len > 20 without an LDS form, a
+ * candidate set over the build budget -- e.g. max_mismatches 3 on 384 x 16).
+ *   FQTK_SCAN_VALU  one lane per read, the table in SGPRs: 8 VALU instructions per (read, sample, 32 bases)
+ *   FQTK_SCAN_MFMA  int8 matrix instructions count the mismatches of 32 reads x 32 samples at a time and make the packed
+ *                   (mismatches, index) key in the accumulator; any barcode_len, at most 16384 samples
+ * fqtk_matcher_scan_kind() reports what the next scanned batch runs; fqtk_matcher_set_scan_kind(m, FQTK_SCAN_MFMA) pins
+ * the matrix form (FQTK_EINVAL when the table has more than 16384 samples), FQTK_SCAN_VALU the other.  The environment
+ * variable FQTK_SCAN (valu / mfma), read by fqtk_matcher_create, sets the same; unset, the matcher chooses. */
+#define FQTK_SCAN_VALU 0
+#define FQTK_SCAN_MFMA 1
+int fqtk_matcher_scan_kind(const fqtk_matcher *m);
+int fqtk_matcher_set_scan_kind(fqtk_matcher *m, int kind);
+
 /* Replaces one `BarcodeMatcher::assign(&mut self, read_bases: &[u8]) -> Option<BarcodeMatch>` call
  * per template (barcode_matching.rs:165-186; sole call site demux.rs:968) with one call per batch.
  * HOST pointers; synchronous.
