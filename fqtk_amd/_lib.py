@@ -129,6 +129,12 @@ SIGNATURES = [
                                               C.c_void_p, C.c_uint64, C.c_void_p]),
     ("fqtk_matcher_wait", C.c_int, [C.c_void_p, C.c_int]),
     ("fqtk_matcher_counts", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fqtk_matcher_census_enable", C.c_int, [C.c_void_p, C.c_uint64]),
+    ("fqtk_matcher_census_disable", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_census_reset", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_census_totals", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64)]),
+    ("fqtk_matcher_census_top", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("fqtk_matchers_allreduce_counts", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
     # include/fqtk_bgzf.h
     ("fqtk_bgzf_last_error", C.c_char_p, []),

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
@@ -51,6 +51,14 @@ class BarcodeMatch:
     best_match: int
     best_mismatches: int
     next_best_mismatches: int
+
+
+class CensusTotals(NamedTuple):
+    """fqtk_matcher_census_totals: keyed + unkeyed + overflow == None results since enable_census() / reset_census()."""
+    distinct: int
+    keyed: int
+    unkeyed: int
+    overflow: int
 
 
 class BarcodeMatcher:
@@ -208,6 +216,32 @@ class BarcodeMatcher:
         handle (e.g. torch.cuda.current_stream().cuda_stream).  Asynchronous."""
         _check(self._lib.fqtk_matcher_assign_batch_device(self._h, d_obs, stride, d_lens or None, n,
                                                           d_out, d_counts or None, stream or None))
+
+    # ---- census of the unmatched barcodes (fqtk_matcher_census_*) -----------------------------------------------
+    def enable_census(self, capacity: int = 0) -> None:
+        """From here on every None read of every batch is tallied on the device by its barcode (0: 2^20 table slots)."""
+        _check(self._lib.fqtk_matcher_census_enable(self._h, int(capacity)))
+
+    def disable_census(self) -> None:
+        _check(self._lib.fqtk_matcher_census_disable(self._h))
+
+    def reset_census(self) -> None:
+        _check(self._lib.fqtk_matcher_census_reset(self._h))
+
+    def census_totals(self) -> CensusTotals:
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(self._lib.fqtk_matcher_census_totals(self._h, *[C.byref(x) for x in v]))
+        return CensusTotals(*[int(x.value) for x in v])
+
+    def census_top(self, k: int) -> list:
+        """The k most frequent unmatched barcodes as [(barcode, templates)], count descending, ties by barcode ascending."""
+        L = self.barcode_len
+        k = min(int(k), self.census_totals().distinct)
+        names = np.empty((max(k, 1), L), dtype="S1")
+        cnt = np.zeros(max(k, 1), dtype=np.uint64)
+        n = C.c_uint32(0)
+        _check(self._lib.fqtk_matcher_census_top(self._h, k, names.ctypes.data, cnt.ctypes.data, C.byref(n)))
+        return [(names[i].tobytes().decode("ascii"), int(cnt[i])) for i in range(int(n.value))]
 
     def poll_error(self, stream: int = 0) -> None:
         idx = C.c_uint64(0)

@@ -37,6 +37,7 @@ extern "C" int fqtk_dev_phase_cycles(unsigned long long *out16) {
 #include "lds_memo_plan.hpp"
 #include "direct_memo_plan.hpp"
 #include "mfma_scan_kernels.hip.h"
+#include "census_kernels.hip.h"
 
 namespace {
 
@@ -189,6 +190,7 @@ struct fqtk_matcher {
     uint8_t *d_mfma_rows = nullptr;            // sample operand, [ntiles * 32][rs]
     fqtk::MfmaScanPlan mfma{};
     int scan_kind_wanted = -1;                 // -1 = auto, else FQTK_SCAN_VALU / FQTK_SCAN_MFMA (FQTK_SCAN, set_scan_kind)
+    fqtk::Census census;                       // opt-in table of the unmatched barcodes (census_kernels.hip.h); off: nothing allocated
     Slot slots[kNumSlots];
 };
 
@@ -741,7 +743,7 @@ int launch_memo(const fqtk_matcher *m, const fqtk::MatchParams &P, hipStream_t s
 
 // One batch: the memo kernel (or the scan, or the all-None fill) and, behind a memo kernel, the second pass.
 // `wl` = the worklist of the stream the batch runs on (batches on different streams may overlap).
-int launch(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t stream, Worklist &wl) {
+int launch_match(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t stream, Worklist &wl) {
     const bool memo = m->use_cache && P0.stride >= P0.L && ((m->d_ldsm && m->memo_kind_wanted != 1) || m->d_memo);
     if (!memo || P0.n > 0xFFFFFFFFull) return launch_memo(m, P0, stream);
     // The list and the second launch only once a read with an IUPAC / junk byte has been met (MatchParams::seen);
@@ -783,6 +785,14 @@ int launch(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t strea
     const int rc = launch_memo(m, P, stream);
     if (rc != FQTK_OK || !P.work_segs) return rc;
     return launch_second_pass(m, P, stream);
+}
+
+// Every entry point's batch goes through here: the matcher's kernels and, with the census on, census_kernel behind them on the
+// same stream (out[] is final there).  Census off: this one branch.
+int launch(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t stream, Worklist &wl) {
+    const int rc = launch_match(m, P0, stream, wl);
+    if (rc != FQTK_OK || !m->census.on()) return rc;
+    return fqtk::census_launch(m->census, P0, m->num_cus, stream);
 }
 
 // The worklist of a caller's stream (the *_device entry point).  A handful of streams at most in practice;
@@ -1543,6 +1553,7 @@ void fqtk_matcher_destroy(fqtk_matcher *m) {
     if (m->d_hot2) (void)hipFree(m->d_hot2);
     if (m->d_ldsm) (void)hipFree(m->d_ldsm);
     if (m->d_mfma_rows) (void)hipFree(m->d_mfma_rows);
+    (void)fqtk::census_disable(m->census);
     if (m->d_table) (void)hipFree(m->d_table);
     if (m->d_lut) (void)hipFree(m->d_lut);
     if (m->d_err) (void)hipFree(m->d_err);
@@ -1603,6 +1614,37 @@ int fqtk_matcher_set_scan_kind(fqtk_matcher *m, int kind) {
     }
     m->scan_kind_wanted = kind;
     return FQTK_OK;
+}
+
+// ---- census of the unmatched barcodes (census_kernels.hip.h) ----------------------------------------------------------
+int fqtk_matcher_census_enable(fqtk_matcher *m, uint64_t capacity_slots) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::census_enable(m->census, m->L, capacity_slots);
+}
+
+int fqtk_matcher_census_disable(fqtk_matcher *m) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::census_disable(m->census);
+}
+
+int fqtk_matcher_census_reset(fqtk_matcher *m) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::census_reset(m->census);
+}
+
+int fqtk_matcher_census_totals(fqtk_matcher *m, uint64_t *distinct, uint64_t *keyed, uint64_t *unkeyed, uint64_t *overflow) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::census_totals(m->census, distinct, keyed, unkeyed, overflow);
+}
+
+int fqtk_matcher_census_top(fqtk_matcher *m, uint32_t k, char *barcodes, uint64_t *counts, uint32_t *n_out) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::census_top(m->census, m->L, k, barcodes, counts, n_out);
 }
 
 int fqtk_matcher_assign_batch_device(fqtk_matcher *m, const void *d_obs, uint32_t stride,

@@ -197,6 +197,7 @@ struct Options {
     bool host_output = false;        // --host-output: format and compress the records on the host (the reference's way)
     bool host_inflate = false;       // --host-inflate: BGZF inputs are inflated by the reader threads even where the device could
     bool gpu_gunzip = false;         // --gpu-gunzip: single-stream gzip inputs are decoded on the device in chunks
+    unsigned long top_unmatched = 0; // --top-unmatched N: census of the unmatched barcodes on the device, N rows in unmatched-barcodes.txt
 };
 
 const char *kUsage =
@@ -228,7 +229,10 @@ const char *kUsage =
     "                                              are, a wavefront each; serial gzip files (gzip, bcl2fastq), from 64 MB of them, in chunks of\n"
     "                                              64 KiB cut at DEFLATE block starts the device finds, windows handed down the chain; what cannot\n"
     "                                              be cut or decoded like that is decoded by a host thread -- any valid file is read (additive flag)\n"
-    "      --gpu-gunzip                            serial gzip inputs on the device whatever their size (additive flag)\n";
+    "      --gpu-gunzip                            serial gzip inputs on the device whatever their size (additive flag)\n"
+    "      --top-unmatched <N>                     tally the sample barcodes of the unmatched templates on the device and write the N most\n"
+    "                                              frequent to <OUTPUT>/unmatched-barcodes.txt (barcode, templates) [default: 0: no tally,\n"
+    "                                              no file]; sample barcodes of at most 32 bases (additive flag)\n";
 
 bool parse_ulong(const std::string &s, unsigned long *out) {
     if (s.empty()) return false;
@@ -317,6 +321,7 @@ Options parse_args(int argc, char **argv) {
         else if (a == "--host-output" || a == "--no-gpu-bgzf") o.host_output = true;
         else if (a == "--host-inflate") o.host_inflate = true;
         else if (a == "--gpu-gunzip") o.gpu_gunzip = true;
+        else if (a == "--top-unmatched") num(&o.top_unmatched);
         else if (a == "--help" || a == "-h") { std::fputs(kUsage, stdout); std::exit(0); }
         else die("unexpected argument '" + a + "' found\n\n" + kUsage);
     }
@@ -551,6 +556,46 @@ bool gpu_output_supported(const Plan &plan, std::string *why) {
     return true;
 }
 
+// --top-unmatched: the census of every device's matcher is switched on right after the matcher exists ...
+void enable_census(fqtk_matcher *m, const Options &opt) {
+    if (opt.top_unmatched && fqtk_matcher_census_enable(m, 0) != FQTK_OK) die(std::string("cannot set up the census of unmatched barcodes: ") + fqtk_last_error());
+}
+
+// ... and read out after the run: every device's entries whole (k = distinct), summed by barcode on the host (a device may be
+// named twice, and the same barcode turns up on every device), ordered -- templates descending, then barcode -- and cut to N rows.
+void write_top_unmatched(const Options &opt, const std::vector<fqtk_matcher *> &matchers, uint32_t L) {
+    if (!opt.top_unmatched) return;
+    std::map<std::string, uint64_t> sum;
+    uint64_t tot[4] = {0, 0, 0, 0};   // distinct (after merging), keyed, unkeyed, overflow
+    for (fqtk_matcher *m : matchers) {
+        uint64_t d = 0, k = 0, u = 0, o = 0;
+        if (fqtk_matcher_census_totals(m, &d, &k, &u, &o) != FQTK_OK) die(fqtk_last_error());
+        std::vector<char> names((size_t)std::max<uint64_t>(d, 1) * L);
+        std::vector<uint64_t> counts((size_t)std::max<uint64_t>(d, 1));
+        uint32_t n = 0;
+        if (fqtk_matcher_census_top(m, (uint32_t)d, names.data(), counts.data(), &n) != FQTK_OK) die(fqtk_last_error());
+        for (uint32_t i = 0; i < n; ++i) sum[std::string(names.data() + (size_t)i * L, L)] += counts[i];
+        tot[1] += k; tot[2] += u; tot[3] += o;
+    }
+    tot[0] = sum.size();
+    std::vector<std::pair<std::string, uint64_t>> rows(sum.begin(), sum.end());   // by barcode; a stable sort keeps that among equals
+    std::stable_sort(rows.begin(), rows.end(), [](const std::pair<std::string, uint64_t> &a, const std::pair<std::string, uint64_t> &b) { return a.second > b.second; });
+    if (rows.size() > opt.top_unmatched) rows.resize(opt.top_unmatched);
+    const std::string path = opt.output + "/unmatched-barcodes.txt";
+    {
+        std::lock_guard<std::mutex> lk(g_created_mu);
+        g_created.push_back(path);
+    }
+    std::string text = "barcode\ttemplates\n";
+    for (const auto &r : rows) text += r.first + "\t" + std::to_string(r.second) + "\n";
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) die("cannot create " + path + ": " + std::strerror(errno));
+    write_all(fd, reinterpret_cast<const uint8_t *>(text.data()), text.size(), path);
+    if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
+    info("Unmatched barcodes: %llu distinct, %llu templates tallied by barcode, %llu without a key (length, junk bytes), %llu beyond the table; top %zu in %s.",
+         (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3], rows.size(), path.c_str());
+}
+
 [[noreturn]] void run_gpu_output(const Options &opt, const Plan &plan, const std::vector<Sample> &samples,
                                  std::vector<std::unique_ptr<FastqSource>> &sources, bool skip_few) {
     const size_t n_inputs = plan.rs.size(), S = samples.size(), G = opt.devices.size();
@@ -656,6 +701,7 @@ bool gpu_output_supported(const Plan &plan, std::string *why) {
             if (fqtk_matcher_create(bc.data(), (uint32_t)S, L, (uint8_t)opt.max_mismatches, (uint8_t)opt.min_mismatch_delta, opt.devices[g], &matchers[g]) != FQTK_OK)
                 die(std::string("cannot create the GPU barcode matcher: ") + fqtk_last_error());
             fqtk_matcher_set_sample_ids(matchers[g], ids.data());
+            enable_census(matchers[g], opt);
             if (g_timing) info("(timing) matcher on device %d created; anonymous resident memory %zu MB.", opt.devices[g], rss_anon_mb());
             fqtk_demux_config cfg;
             std::memset(&cfg, 0, sizeof cfg);
@@ -1505,6 +1551,7 @@ bool gpu_output_supported(const Plan &plan, std::string *why) {
     update_metrics(rows, unmatched);
     rows.push_back(unmatched);
     std::string err;
+    write_top_unmatched(opt, matchers, L);
     if (!write_metrics_tsv(opt.output + "/demux-metrics.txt", rows, &err)) die(err);
     end_process();
 }
@@ -1581,6 +1628,13 @@ int main(int argc, char **argv) {
     }
     for (const std::string &in : opt.inputs)
         if (access(in.c_str(), F_OK) != 0) problems.push_back("Provided input file \"" + in + "\" doesn't exist");
+    if (opt.top_unmatched) {   // the census keys at most 32 bases: said here, before any input is opened (a sheet that does not load is reported below)
+        std::vector<Sample> sheet;
+        std::string err;
+        if (load_samples(opt.sample_metadata, &sheet, &err) && !sheet.empty() && sheet[0].barcode.size() > 32)
+            die("invalid value for '--top-unmatched': the census of unmatched barcodes takes sample barcodes of at most 32 bases, those of \"" +
+                opt.sample_metadata + "\" have " + std::to_string(sheet[0].barcode.size()));
+    }
     std::vector<std::unique_ptr<FastqSource>> sources;
     // Single-stream gzip inputs are decoded by several threads each (parallel_gunzip.hpp): three quarters of the usable
     // CPUs, shared out by file size (the index reads of a run are a fifth of its bytes), at most 8 per file.
@@ -1677,6 +1731,7 @@ int main(int argc, char **argv) {
             std::vector<const char *> ids;   // so that a length error names the sample like the reference's panic does
             for (const Sample &s : samples) ids.push_back(s.sample_id.c_str());
             fqtk_matcher_set_sample_ids(matchers[g], ids.data());
+            enable_census(matchers[g], opt);
             info("GPU barcode matcher ready on device %d (%llu memo entries).", opt.devices[g],
                  (unsigned long long)fqtk_matcher_memo_entries(matchers[g]));
         }
@@ -2160,6 +2215,7 @@ int main(int argc, char **argv) {
     update_metrics(rows, unmatched);
     rows.push_back(unmatched);
     std::string err;
+    write_top_unmatched(opt, matchers, L);
     if (!write_metrics_tsv(opt.output + "/demux-metrics.txt", rows, &err)) die(err);
     // Everything is on disk and closed.  The process ends here: tearing the HIP runtime down through the
     // matcher's destructor and the atexit handlers costs ~0.25 s and frees nothing the OS does not free.

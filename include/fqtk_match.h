@@ -226,7 +226,44 @@ int fqtk_matcher_wait(fqtk_matcher *m, int slot);
  * and resets the device accumulator.  Synchronises all slots. */
 int fqtk_matcher_counts(fqtk_matcher *m, uint64_t *counts);
 
-/* ---- several GPUs in one process ------------------------------------------------ */
+/* ---- census of the unmatched barcodes: which barcodes did the None reads carry? ----------------------------------
+ * No counterpart in the reference (its only figure is the `unmatched` row of demux-metrics.txt, counts[S] here).  Opt-in,
+ * owned by the handle: a device-resident table of (barcode, count) over every read whose result is None, accumulated over
+ * every batch of every entry point above (and of the record pipeline of fqtk_demux.h, which runs its batches through
+ * fqtk_matcher_assign_batch_device) by one more kernel behind the batch's own, on the batch's stream.  OFF (the default):
+ * no kernel is launched, no memory is taken and every result, count and error is what it is without these entry points.
+ *   keyed    a None read of exactly barcode_len bases (no obs_len, or obs_len[i] == barcode_len) none of whose first
+ *            barcode_len bytes enc() maps to 0.  Its KEY is its enc() string, 4 bits a base: lower case is upper case, 'N' 'n'
+ *            '.' are N, U is T, IUPAC codes keep their mask; two reads are the same barcode iff their keys are equal, and the
+ *            barcode is reported as the reference's decode() spells the key (mod.rs:68): barcode_len letters of
+ *            ACGTMRWSYKVHDBN.  Reads the no-call prefilter rejects are keyed like any other; all-N is an ordinary entry.
+ *   unkeyed  every other None read -- shorter or longer than barcode_len (a read that raises FQTK_ELEN too), one with a junk
+ *            byte, every read of a batch with stride < barcode_len -- adds 1 to one counter.
+ *   overflow the table has `capacity` slots, fixed at enable.  A read whose key finds no slot within the kernel's bounded
+ *            probe sequence adds 1 to `overflow` and is not stored.
+ * A barcode that is reported carries its EXACT count and is reported once: slots only ever go from empty to a key, probing
+ * is deterministic, so a key that was dropped once is dropped every time.  At any quiescent point
+ *   keyed + unkeyed + overflow == number of None results produced since enable / reset,   keyed = sum of the stored counts.
+ * barcode_len <= 32 (one or two 64-bit key words; covers 8 + 8 .. 16 + 16 dual indexes).
+ * Device memory (what rocm-smi shows for the process grows by this at enable): capacity x 16 bytes for barcode_len <= 16,
+ * capacity x 24 above; the default of 2^20 slots is 16 / 24 MiB.  A read-out adds, while it runs, 24 bytes per distinct barcode.
+ *
+ * enable: capacity_slots is rounded up to a power of two, 0 = 2^20; allocates and clears (again with another capacity:
+ * re-allocates and clears).  FQTK_EINVAL when barcode_len > 32 or capacity_slots > 2^32; FQTK_ENOMEM.
+ * disable frees the table (fqtk_matcher_destroy does, too); reset clears the table and the totals.  All three wait for the
+ * device to drain first. */
+int fqtk_matcher_census_enable(fqtk_matcher *m, uint64_t capacity_slots);
+int fqtk_matcher_census_disable(fqtk_matcher *m);
+int fqtk_matcher_census_reset(fqtk_matcher *m);
+/* The two read-outs synchronise the device first, leave the census as it is, and return FQTK_EINVAL ("census is not enabled")
+ * when it is off.  totals: distinct = barcodes stored; any pointer may be NULL. */
+int fqtk_matcher_census_totals(fqtk_matcher *m, uint64_t *distinct, uint64_t *keyed, uint64_t *unkeyed, uint64_t *overflow);
+/* top: the k most frequent barcodes, count descending, ties by the barcode ascending (bytewise).  barcodes: room for
+ * k x barcode_len bytes, row i at barcodes + i * barcode_len, no NUL; counts: k; *n_out = rows written = min(k, distinct).
+ * Only the `distinct` entries cross the link; the order is made on the host. */
+int fqtk_matcher_census_top(fqtk_matcher *m, uint32_t k, char *barcodes, uint64_t *counts, uint32_t *n_out);
+
+/* ---- several GPUs in one process------------------------------------------------ */
 /* Templates are independent, so chunks shard over devices with no data-path exchange: one matcher per
  * device (the table is replicated by fqtk_matcher_create), chunk k goes to matcher k mod n.  The ONE
  * collective of the path is the end-of-run reduction of the per-sample counts (the `templates` column of
