@@ -65,6 +65,7 @@ class fqtk_demux_result(C.Structure):
 
 
 FQTK_DEMUX_SLOTS, FQTK_DEMUX_STAGES = 3, 8
+FQTK_DEMUX_QUALITY_LDS_COUNTERS = 8192   # tables of up to this many counters are summed in LDS first (quality_kernels.hip.h)
 
 
 _lib = None
@@ -159,6 +160,9 @@ SIGNATURES = [
     ("fqtk_demuxer_record_text", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     ("fqtk_demuxer_flush", C.c_int, [C.c_void_p, C.POINTER(fqtk_demux_result)]),
     ("fqtk_demuxer_counts", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fqtk_demuxer_quality_enable", C.c_int, [C.c_void_p]),
+    ("fqtk_demuxer_quality_row_words", C.c_uint32, [C.c_void_p]),
+    ("fqtk_demuxer_quality", C.c_int, [C.c_void_p, C.c_void_p]),
     ("fqtk_demuxer_stage_seconds", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("fqtk_demuxer_stage_name", C.c_char_p, [C.c_int]),
     ("fqtk_demuxer_feed", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),

@@ -29,6 +29,7 @@
 #include "demux_kernels.hip.h"
 #include "inflate_internal.hpp"
 #include "matcher_internal.hpp"
+#include "quality_kernels.hip.h"
 
 namespace {
 using namespace fqtk::demux;
@@ -194,6 +195,13 @@ struct fqtk_demuxer {
                                         // round robin (measured with decoder wavefronts on the CUs: 14.3 vs 16.9 M templates/s steady from gzip inputs, 45.0 vs 47.2 from text)
     bool ranked = false;                // stream priorities in use
     int feed_priority = 0;
+    // per-sample yield and quality tally (fqtk_demuxer_quality_enable): level 2 of quality_kernels.hip.h
+    bool quality = false;
+    QualConfig Q{};
+    unsigned long long *d_qual = nullptr;   // [n_samples + 1][Q.row_words]
+    uint32_t qual_grid = 0;                 // FQTK_QUALITY_GRID=k (tests, A/B runs): at most k workgroups, so that a small chunk takes many rounds
+    std::vector<fqtk_demux_segment> t_segs; // the T segments of all inputs as configured, in input order, wanted as files or not
+    std::vector<uint32_t> t_seg_input;      // ... and whose each is
 };
 
 namespace {
@@ -355,6 +363,7 @@ int fqtk_demuxer_create(fqtk_matcher *m, const fqtk_demux_config *cfg, fqtk_demu
             int ty = -1;
             for (int q = 0; q < 4; ++q) if (sg.kind == kKinds[q]) ty = q;
             if (ty < 0) { if (sg.kind == 'S') continue; delete d; return set_error(FQTK_EINVAL, "unknown segment kind"); }
+            if (ty == 0) { d->t_segs.push_back(sg); d->t_seg_input.push_back(i); }
             by_type[ty].push_back(fqtk::fmt::FileSeg{i, sg.offset, sg.length, ++per_type[ty]});
         }
         C.min_len[i] = min_len;
@@ -460,6 +469,7 @@ void fqtk_demuxer_destroy(fqtk_demuxer *d) {
     if (d->d_persist) (void)hipFree(d->d_persist);
     if (d->d_fs) (void)hipFree(d->d_fs);
     if (d->d_counts) (void)hipFree(d->d_counts);
+    if (d->d_qual) (void)hipFree(d->d_qual);
     if (d->d_tok) (void)hipFree(d->d_tok);
     for (hipStream_t st : {d->s_in, d->s_a, d->s_b, d->s_out}) if (st) (void)hipStreamDestroy(st);
     delete d;
@@ -595,6 +605,15 @@ static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, 
                        s.rec_off.p, s.tile_tot.p, s.fc.p, d->d_persist, s.slabs.p, s.d_status);
     DX_TRY(hipGetLastError());
     DX_TRY(hipEventRecord(s.ev[4], A));
+    if (d->quality) {   // (before ev_fmt as well: it reads the window's text)
+        const uint64_t items = (uint64_t)n * d->Q.items;
+        const uint32_t n_counters = (C.n_samples + 1u) * d->Q.row_words;
+        const uint32_t use_lds = n_counters <= kQualLdsCounters ? 1u : 0u;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((items + kQualGroups - 1) / kQualGroups, d->qual_grid ? d->qual_grid : (uint64_t)d->num_cus * 8u);
+        hipLaunchKernelGGL(k_quality, dim3(grid), dim3(kQualBlock), use_lds ? n_counters * sizeof(uint32_t) : 0, A, T, d->Q, n, (const uint32_t *)s.res.p,
+                           (const uint8_t *)s.skip.p, d->d_qual, n_counters, use_lds, (const ChunkStatus *)s.d_status);
+        DX_TRY(hipGetLastError());
+    }
     if (T.window) {   // (before ev_fmt: the arena the window lies in may be reused once that event is reached)
         hipLaunchKernelGGL(k_save_error_text, dim3(2 * C.n_inputs), dim3(64), 0, A, T, C.n_inputs, n, (const ChunkStatus *)s.d_status, s.d_err_text);
         DX_TRY(hipGetLastError());
@@ -1421,6 +1440,52 @@ int fqtk_demuxer_counts(fqtk_demuxer *d, uint64_t *counts) {
     std::vector<unsigned long long> h((size_t)d->C.n_samples + 1);
     DX_TRY(hipMemcpy(h.data(), d->d_counts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < h.size(); ++i) counts[i] += (uint64_t)h[i];
+    return FQTK_OK;
+}
+
+int fqtk_demuxer_quality_enable(fqtk_demuxer *d) {
+    if (!d) return set_error(FQTK_EINVAL, "NULL argument");
+    if (d->quality) return FQTK_OK;
+    if (d->chunk_no) return set_error(FQTK_EINVAL, "the quality tally is enabled before the first chunk is submitted");
+    if (d->t_segs.size() > kQualMaxSegs) return set_error(FQTK_EINVAL, "the quality tally takes at most 32 template segments over all inputs");
+    QualConfig &Q = d->Q;
+    std::memset(&Q, 0, sizeof Q);
+    Q.n_inputs = d->C.n_inputs;
+    Q.n_samples = d->C.n_samples;
+    Q.row_words = 3u + 4u * d->C.n_inputs;
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < d->C.n_inputs; ++i) {   // (t_segs is in input order)
+        const uint32_t first = k;
+        for (size_t q = 0; q < d->t_segs.size(); ++q)
+            if (d->t_seg_input[q] == i) { Q.t_off[k] = d->t_segs[q].offset; Q.t_len[k] = d->t_segs[q].length; ++k; }
+        if (k == first) continue;
+        Q.qin[Q.n_qin] = (uint8_t)i;
+        Q.seg0[Q.n_qin] = (uint8_t)first;
+        Q.seg0[++Q.n_qin] = (uint8_t)k;
+    }
+    Q.items = std::max<uint32_t>(Q.n_qin, 1u);
+    {
+        const char *e = std::getenv("FQTK_QUALITY_GRID");
+        d->qual_grid = e && *e ? (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 10), 1u << 16) : 0u;
+    }
+    DX_TRY(hipSetDevice(d->device));
+    const size_t bytes = ((size_t)Q.n_samples + 1) * Q.row_words * sizeof(unsigned long long);
+    DX_TRY(hipMalloc(reinterpret_cast<void **>(&d->d_qual), bytes));
+    DX_TRY(hipMemset(d->d_qual, 0, bytes));
+    d->quality = true;
+    return FQTK_OK;
+}
+
+uint32_t fqtk_demuxer_quality_row_words(const fqtk_demuxer *d) { return d ? 3u + 4u * d->C.n_inputs : 0u; }
+
+int fqtk_demuxer_quality(fqtk_demuxer *d, uint64_t *out) {
+    if (!d || !out) return set_error(FQTK_EINVAL, "NULL argument");
+    if (!d->quality) return set_error(FQTK_EINVAL, "the quality tally was not enabled (fqtk_demuxer_quality_enable)");
+    DX_TRY(hipSetDevice(d->device));
+    DX_TRY(hipStreamSynchronize(d->s_a));
+    std::vector<unsigned long long> h(((size_t)d->C.n_samples + 1) * d->Q.row_words);
+    DX_TRY(hipMemcpy(h.data(), d->d_qual, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) out[i] += (uint64_t)h[i];
     return FQTK_OK;
 }
 

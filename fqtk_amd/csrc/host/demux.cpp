@@ -49,6 +49,7 @@
 #include "fastq_io.hpp"
 #include "header.hpp"
 #include "metrics.hpp"
+#include "quality.hpp"
 #include "read_structure.hpp"
 #include "region_inflate.hpp"
 #include "samples.hpp"
@@ -198,6 +199,7 @@ struct Options {
     bool host_inflate = false;       // --host-inflate: BGZF inputs are inflated by the reader threads even where the device could
     bool gpu_gunzip = false;         // --gpu-gunzip: single-stream gzip inputs are decoded on the device in chunks
     unsigned long top_unmatched = 0; // --top-unmatched N: census of the unmatched barcodes on the device, N rows in unmatched-barcodes.txt
+    bool quality_metrics = false;    // --quality-metrics: per-sample yield and quality in demux-quality-metrics.txt
 };
 
 const char *kUsage =
@@ -232,7 +234,10 @@ const char *kUsage =
     "      --gpu-gunzip                            serial gzip inputs on the device whatever their size (additive flag)\n"
     "      --top-unmatched <N>                     tally the sample barcodes of the unmatched templates on the device and write the N most\n"
     "                                              frequent to <OUTPUT>/unmatched-barcodes.txt (barcode, templates) [default: 0: no tally,\n"
-    "                                              no file]; sample barcodes of at most 32 bases (additive flag)\n";
+    "                                              no file]; sample barcodes of at most 32 bases (additive flag)\n"
+    "      --quality-metrics                       tally yield and quality per sample and read over the template segments -- templates, perfect and\n"
+    "                                              one-mismatch barcode matches, bases, bases at or above Q20 / Q30, mean quality -- and write\n"
+    "                                              <OUTPUT>/demux-quality-metrics.txt; on the device unless --host-output (additive flag)\n";
 
 bool parse_ulong(const std::string &s, unsigned long *out) {
     if (s.empty()) return false;
@@ -322,6 +327,7 @@ Options parse_args(int argc, char **argv) {
         else if (a == "--host-inflate") o.host_inflate = true;
         else if (a == "--gpu-gunzip") o.gpu_gunzip = true;
         else if (a == "--top-unmatched") num(&o.top_unmatched);
+        else if (a == "--quality-metrics") o.quality_metrics = true;
         else if (a == "--help" || a == "-h") { std::fputs(kUsage, stdout); std::exit(0); }
         else die("unexpected argument '" + a + "' found\n\n" + kUsage);
     }
@@ -596,6 +602,23 @@ void write_top_unmatched(const Options &opt, const std::vector<fqtk_matcher *> &
          (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3], rows.size(), path.c_str());
 }
 
+// --quality-metrics: the table (summed over devices, or over the router threads) as demux-quality-metrics.txt
+void write_quality_metrics(const Options &opt, const Plan &plan, const std::vector<Sample> &samples, const QualityTable &table) {
+    std::vector<std::string> ids, barcodes;
+    for (const Sample &s : samples) { ids.push_back(s.sample_id); barcodes.push_back(s.barcode); }
+    ids.push_back(opt.unmatched_prefix);
+    barcodes.push_back(".");
+    const std::string path = opt.output + "/demux-quality-metrics.txt", text = quality_tsv(table, plan.rs, ids, barcodes);
+    {
+        std::lock_guard<std::mutex> lk(g_created_mu);
+        g_created.push_back(path);
+    }
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) die("cannot create " + path + ": " + std::strerror(errno));
+    write_all(fd, reinterpret_cast<const uint8_t *>(text.data()), text.size(), path);
+    if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
+}
+
 [[noreturn]] void run_gpu_output(const Options &opt, const Plan &plan, const std::vector<Sample> &samples,
                                  std::vector<std::unique_ptr<FastqSource>> &sources, bool skip_few) {
     const size_t n_inputs = plan.rs.size(), S = samples.size(), G = opt.devices.size();
@@ -714,6 +737,7 @@ void write_top_unmatched(const Options &opt, const std::vector<fqtk_matcher *> &
             cfg.carry_blocks = G == 1 ? 1 : 0;   // several devices take the chunks in turn: a file's stream must not wait on any of them
             cfg.compression_level = (int)opt.compression_level;
             if (fqtk_demuxer_create(matchers[g], &cfg, &demuxers[g]) != FQTK_OK) die(std::string("cannot set up the GPU record pipeline: ") + fqtk_last_error());
+            if (opt.quality_metrics && fqtk_demuxer_quality_enable(demuxers[g]) != FQTK_OK) die(std::string("cannot set up the quality metrics: ") + fqtk_last_error());
             info("GPU barcode matcher and record pipeline ready on device %d (%llu memo entries).", opt.devices[g],
                  (unsigned long long)fqtk_matcher_memo_entries(matchers[g]));
             if (g_timing) info("(timing) anonymous resident memory: %zu MB.", rss_anon_mb());
@@ -1552,6 +1576,15 @@ void write_top_unmatched(const Options &opt, const std::vector<fqtk_matcher *> &
     rows.push_back(unmatched);
     std::string err;
     write_top_unmatched(opt, matchers, L);
+    if (opt.quality_metrics) {   // the devices' tables, summed (fqtk_demuxer_quality ADDS)
+        QualityTable qt;
+        qt.init(S, n_inputs);
+        for (size_t g = 0; g < G; ++g)
+            if (fqtk_demuxer_quality(demuxers[g], qt.v.data()) != FQTK_OK) die(fqtk_last_error());
+        for (size_t s = 0; s <= S; ++s)
+            if (qt.row(s)[0] != counts[s]) die("internal error: the quality metrics' template counts differ from the per-sample counts");
+        write_quality_metrics(opt, plan, samples, qt);
+    }
     if (!write_metrics_tsv(opt.output + "/demux-metrics.txt", rows, &err)) die(err);
     end_process();
 }
@@ -1867,6 +1900,11 @@ int main(int argc, char **argv) {
     // unmatched pair alone takes 10-20 % of the records -- and a modulo assignment left one router with twice the
     // work of the others.  Written once by the main thread before chunk 0 is handed to the routers.
     std::vector<uint16_t> file_owner(n_outs, 0);
+    // --quality-metrics on this path: router w tallies the templates of the samples s with s mod n_workers == w into a table of
+    // its own (it walks the chunk's templates anyway), and the tables are summed when the routers end
+    QualityTable quality_total;
+    std::mutex quality_mu;
+    if (opt.quality_metrics) quality_total.init(S, n_inputs);
     std::vector<std::thread> workers;
     for (size_t w = 0; w < n_workers; ++w)
         workers.emplace_back([&, w] {
@@ -1875,6 +1913,10 @@ int main(int argc, char **argv) {
             bool have_plan = false;
             std::vector<std::string_view> bsegs, msegs;
             std::vector<uint32_t> mine;
+            QualityTable quality;
+            std::vector<const char *> qual_of(n_inputs);
+            std::vector<uint32_t> len_of(n_inputs);
+            if (opt.quality_metrics) quality.init(S, n_inputs);
             for (;;) {
                 const uint64_t tw = tick();
                 std::shared_ptr<Chunk> ch = wq[w]->pop();
@@ -1901,6 +1943,10 @@ int main(int argc, char **argv) {
                     if (ch->skip[i]) continue;
                     const size_t s = ch->res[i].idx == FQTK_NO_MATCH ? S : ch->res[i].idx;
                     if (!owned[s].empty()) mine.push_back((uint32_t)i);
+                    if (opt.quality_metrics && s % n_workers == w) {
+                        for (size_t b = 0; b < n_inputs; ++b) { qual_of[b] = ch->batches[b]->qual(i); len_of[b] = ch->batches[b]->recs[i].seq_len; }
+                        add_template(quality.row(s), ch->res[i].idx != FQTK_NO_MATCH, ch->res[i].best, plan.rs, qual_of.data(), len_of.data());
+                    }
                 }
                 auto prefetch_template = [&](size_t i) {
                     for (size_t b = 0; b < ch->batches.size(); ++b) {
@@ -1955,6 +2001,10 @@ int main(int argc, char **argv) {
             }
             for (size_t f = 0; f < outs.size(); ++f)
                 if (file_owner[f] == w) submit_blocks(outs[f], jobs, true);
+            if (opt.quality_metrics) {
+                std::lock_guard<std::mutex> lk(quality_mu);
+                quality_total.add(quality);
+            }
         });
 
     // ---- stage B (this thread): chunk assembly, barcode SoA packing, GPU pipeline -------------------
@@ -2216,6 +2266,11 @@ int main(int argc, char **argv) {
     rows.push_back(unmatched);
     std::string err;
     write_top_unmatched(opt, matchers, L);
+    if (opt.quality_metrics) {
+        for (size_t s = 0; s <= S; ++s)
+            if (quality_total.row(s)[0] != counts[s]) die("internal error: the quality metrics' template counts differ from the per-sample counts");
+        write_quality_metrics(opt, plan, samples, quality_total);
+    }
     if (!write_metrics_tsv(opt.output + "/demux-metrics.txt", rows, &err)) die(err);
     // Everything is on disk and closed.  The process ends here: tearing the HIP runtime down through the
     // matcher's destructor and the atexit handlers costs ~0.25 s and frees nothing the OS does not free.

@@ -211,6 +211,17 @@ class Demuxer:
         _check(self._lib.fqtk_demuxer_counts(self._h, c.ctypes.data))
         return c
 
+    def enable_quality(self) -> None:
+        """Per-sample yield and quality metrics are tallied on the device from the next chunk on (before the first submit)."""
+        _check(self._lib.fqtk_demuxer_quality_enable(self._h))
+
+    def quality(self) -> np.ndarray:
+        """[n_samples + 1, 3 + 4 * n_inputs] uint64: templates, perfect_matches, one_mismatch_matches, then per input
+        bases, q20_bases, q30_bases, qual_byte_sum over the template segments (include/fqtk_demux.h); unmatched last."""
+        q = np.zeros((self.matcher.n_samples + 1, int(self._lib.fqtk_demuxer_quality_row_words(self._h))), dtype=np.uint64)
+        _check(self._lib.fqtk_demuxer_quality(self._h, q.ctypes.data))
+        return q
+
     def stage_seconds(self) -> Dict[str, float]:
         s = (C.c_double * _lib.FQTK_DEMUX_STAGES)()
         _check(self._lib.fqtk_demuxer_stage_seconds(self._h, s))

@@ -233,6 +233,21 @@ int fqtk_demuxer_flush(fqtk_demuxer *d, fqtk_demux_result *res);
 /* Adds the per-sample template counts (n_samples + 1, unmatched last) of all collected chunks into counts. */
 int fqtk_demuxer_counts(fqtk_demuxer *d, uint64_t *counts);
 
+/* ---- per-sample yield and quality metrics, tallied on the device (opt-in) ---------------------------------------------------
+ * Once enabled, every chunk adds one row of counters per sample (n_samples + 1 rows, unmatched last) for the templates it
+ * does not drop:
+ *   [0] templates   [1] perfect_matches (matched with 0 mismatches)   [2] one_mismatch_matches (matched with 1)
+ *   then per input i, at 3 + 4 i:  bases, q20_bases (byte >= 53), q30_bases (byte >= 63), qual_byte_sum
+ * over the bytes of input i's quality line that lie in a template (T) segment of its read structure -- the span the T files
+ * get, a trailing '\r' excluded; unsigned compares on the raw Phred+33 byte.  An input without a T segment has four zeros.
+ * Mean quality = qual_byte_sum / bases - 33.  Column 0 equals fqtk_demuxer_counts.  Not enabled: no kernel runs, nothing is
+ * allocated.  At most 32 T segments over all inputs. */
+#define FQTK_DEMUX_QUALITY_LDS_COUNTERS 8192 /* tables of up to this many counters are summed in LDS first, larger ones in HBM directly */
+int fqtk_demuxer_quality_enable(fqtk_demuxer *d);                  /* before the first submit; FQTK_EINVAL after one */
+uint32_t fqtk_demuxer_quality_row_words(const fqtk_demuxer *d);    /* 3 + 4 * n_inputs */
+/* Adds the (n_samples + 1) rows of all collected chunks into out (so several devices sum); FQTK_EINVAL when not enabled. */
+int fqtk_demuxer_quality(fqtk_demuxer *d, uint64_t *out);
+
 /* Seconds of device time per stage, summed over the chunks collected so far (names: fqtk_demuxer_stage_name). */
 #define FQTK_DEMUX_STAGES 8
 int fqtk_demuxer_stage_seconds(fqtk_demuxer *d, double *seconds /* FQTK_DEMUX_STAGES */);
