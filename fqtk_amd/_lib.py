@@ -136,6 +136,12 @@ SIGNATURES = [
     ("fqtk_matcher_census_totals", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]),
     ("fqtk_matcher_census_top", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("fqtk_matcher_pairs_enable", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("fqtk_matcher_pairs_disable", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_pairs_reset", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_pairs_dims", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("fqtk_matcher_pairs_index", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_char_p]),
+    ("fqtk_matcher_pairs_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("fqtk_matchers_allreduce_counts", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
     # include/fqtk_bgzf.h
     ("fqtk_bgzf_last_error", C.c_char_p, []),

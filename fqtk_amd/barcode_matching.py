@@ -243,6 +243,41 @@ class BarcodeMatcher:
         _check(self._lib.fqtk_matcher_census_top(self._h, k, names.ctypes.data, cnt.ctypes.data, C.byref(n)))
         return [(names[i].tobytes().decode("ascii"), int(cnt[i])) for i in range(int(n.value))]
 
+    # ---- index pairs of the unmatched reads (fqtk_matcher_pairs_*) -----------------------------------------------
+    def enable_pairs(self, len_a: int, max_mismatches: Optional[int] = None, min_mismatch_delta: Optional[int] = None) -> None:
+        """From here on every None read of every batch has its two indexes (bases [0, len_a) and [len_a, L)) assigned on their
+        own against the table's distinct indexes, and the pair tallied on the device.  The defaults are the matcher's own values."""
+        mm = self.max_mismatches if max_mismatches is None else max_mismatches
+        delta = self.min_mismatch_delta if min_mismatch_delta is None else min_mismatch_delta
+        _check(self._lib.fqtk_matcher_pairs_enable(self._h, int(len_a), int(mm), int(delta)))
+
+    def disable_pairs(self) -> None:
+        _check(self._lib.fqtk_matcher_pairs_disable(self._h))
+
+    def reset_pairs(self) -> None:
+        _check(self._lib.fqtk_matcher_pairs_reset(self._h))
+
+    def pair_indexes(self) -> tuple:
+        """(A, B): the distinct index-1 and index-2 strings, in the order of the matrix' rows and columns."""
+        u = (C.c_uint32(0), C.c_uint32(0))
+        _check(self._lib.fqtk_matcher_pairs_dims(self._h, C.byref(u[0]), C.byref(u[1])))
+        buf = C.create_string_buffer(self.barcode_len + 1)
+        lists = ([], [])
+        for which in (0, 1):
+            for i in range(int(u[which].value)):
+                _check(self._lib.fqtk_matcher_pairs_index(self._h, which, i, buf))
+                lists[which].append(buf.value.decode("latin-1"))
+        return lists
+
+    def pairs(self) -> tuple:
+        """(matrix uint64 [U_A + 1, U_B + 1], skipped): row U_A / column U_B = that index unassigned; sum + skipped == None results."""
+        u = (C.c_uint32(0), C.c_uint32(0))
+        _check(self._lib.fqtk_matcher_pairs_dims(self._h, C.byref(u[0]), C.byref(u[1])))
+        mat = np.zeros((int(u[0].value) + 1, int(u[1].value) + 1), dtype=np.uint64)
+        skipped = C.c_uint64(0)
+        _check(self._lib.fqtk_matcher_pairs_read(self._h, mat.ctypes.data, C.byref(skipped)))
+        return mat, int(skipped.value)
+
     def poll_error(self, stream: int = 0) -> None:
         idx = C.c_uint64(0)
         _check(self._lib.fqtk_matcher_poll_error(self._h, stream or None, C.byref(idx)))

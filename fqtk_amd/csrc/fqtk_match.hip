@@ -38,6 +38,7 @@ extern "C" int fqtk_dev_phase_cycles(unsigned long long *out16) {
 #include "direct_memo_plan.hpp"
 #include "mfma_scan_kernels.hip.h"
 #include "census_kernels.hip.h"
+#include "pair_kernels.hip.h"
 
 namespace {
 
@@ -191,6 +192,7 @@ struct fqtk_matcher {
     fqtk::MfmaScanPlan mfma{};
     int scan_kind_wanted = -1;                 // -1 = auto, else FQTK_SCAN_VALU / FQTK_SCAN_MFMA (FQTK_SCAN, set_scan_kind)
     fqtk::Census census;                       // opt-in table of the unmatched barcodes (census_kernels.hip.h); off: nothing allocated
+    fqtk::Pairs pairs;                         // opt-in index-pair tally of the unmatched reads (pair_kernels.hip.h); off: nothing allocated
     Slot slots[kNumSlots];
 };
 
@@ -791,8 +793,12 @@ int launch_match(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t
 // same stream (out[] is final there).  Census off: this one branch.
 int launch(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t stream, Worklist &wl) {
     const int rc = launch_match(m, P0, stream, wl);
-    if (rc != FQTK_OK || !m->census.on()) return rc;
-    return fqtk::census_launch(m->census, P0, m->num_cus, stream);
+    if (rc != FQTK_OK || !(m->census.on() || m->pairs.on())) return rc;
+    if (m->census.on()) {
+        const int rc_census = fqtk::census_launch(m->census, P0, m->num_cus, stream);
+        if (rc_census != FQTK_OK) return rc_census;
+    }
+    return m->pairs.on() ? fqtk::pairs_launch(m->pairs, P0, m->num_cus, stream) : FQTK_OK;
 }
 
 // The worklist of a caller's stream (the *_device entry point).  A handful of streams at most in practice;
@@ -1554,6 +1560,7 @@ void fqtk_matcher_destroy(fqtk_matcher *m) {
     if (m->d_ldsm) (void)hipFree(m->d_ldsm);
     if (m->d_mfma_rows) (void)hipFree(m->d_mfma_rows);
     (void)fqtk::census_disable(m->census);
+    (void)fqtk::pairs_disable(m->pairs);
     if (m->d_table) (void)hipFree(m->d_table);
     if (m->d_lut) (void)hipFree(m->d_lut);
     if (m->d_err) (void)hipFree(m->d_err);
@@ -1645,6 +1652,47 @@ int fqtk_matcher_census_top(fqtk_matcher *m, uint32_t k, char *barcodes, uint64_
     if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
     HIP_TRY(hipSetDevice(m->device));
     return fqtk::census_top(m->census, m->L, k, barcodes, counts, n_out);
+}
+
+// ---- index-pair tally of the unmatched reads (pair_kernels.hip.h) ------------------------------------------------------
+int fqtk_matcher_pairs_enable(fqtk_matcher *m, uint32_t len_a, uint32_t max_mismatches, uint32_t min_mismatch_delta) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::pairs_enable(m->pairs, m->barcodes_upper, m->L, len_a, max_mismatches, min_mismatch_delta, enc_byte);
+}
+
+int fqtk_matcher_pairs_disable(fqtk_matcher *m) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::pairs_disable(m->pairs);
+}
+
+int fqtk_matcher_pairs_reset(fqtk_matcher *m) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::pairs_reset(m->pairs);
+}
+
+int fqtk_matcher_pairs_dims(fqtk_matcher *m, uint32_t *u_a, uint32_t *u_b) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    if (!m->pairs.on()) return fail(FQTK_EINVAL, "the index-pair tally is not enabled");
+    if (u_a) *u_a = (uint32_t)m->pairs.index[0].size();
+    if (u_b) *u_b = (uint32_t)m->pairs.index[1].size();
+    return FQTK_OK;
+}
+
+int fqtk_matcher_pairs_index(fqtk_matcher *m, int which, uint32_t i, char *out) {
+    if (!m || !out) return fail(FQTK_EINVAL, "NULL argument");
+    if (!m->pairs.on()) return fail(FQTK_EINVAL, "the index-pair tally is not enabled");
+    if (which < 0 || which > 1 || i >= m->pairs.index[which].size()) return fail(FQTK_EINVAL, "no such index");
+    std::memcpy(out, m->pairs.index[which][i].c_str(), m->pairs.index[which][i].size() + 1);
+    return FQTK_OK;
+}
+
+int fqtk_matcher_pairs_read(fqtk_matcher *m, uint64_t *matrix, uint64_t *skipped) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::pairs_read(m->pairs, matrix, skipped);
 }
 
 int fqtk_matcher_assign_batch_device(fqtk_matcher *m, const void *d_obs, uint32_t stride,

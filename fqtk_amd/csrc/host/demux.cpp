@@ -199,6 +199,8 @@ struct Options {
     bool host_inflate = false;       // --host-inflate: BGZF inputs are inflated by the reader threads even where the device could
     bool gpu_gunzip = false;         // --gpu-gunzip: single-stream gzip inputs are decoded on the device in chunks
     unsigned long top_unmatched = 0; // --top-unmatched N: census of the unmatched barcodes on the device, N rows in unmatched-barcodes.txt
+    bool index_pairs = false;        // --index-pairs: index-1 x index-2 tally of the unmatched templates on the device -> index-pairs.txt
+    uint32_t pairs_len_a = 0;        //   length of the first of the two sample-barcode segments (main() works it out before any input is opened)
     bool quality_metrics = false;    // --quality-metrics: per-sample yield and quality in demux-quality-metrics.txt
 };
 
@@ -237,7 +239,11 @@ const char *kUsage =
     "                                              no file]; sample barcodes of at most 32 bases (additive flag)\n"
     "      --quality-metrics                       tally yield and quality per sample and read over the template segments -- templates, perfect and\n"
     "                                              one-mismatch barcode matches, bases, bases at or above Q20 / Q30, mean quality -- and write\n"
-    "                                              <OUTPUT>/demux-quality-metrics.txt; on the device unless --host-output (additive flag)\n";
+    "                                              <OUTPUT>/demux-quality-metrics.txt; on the device unless --host-output (additive flag)\n"
+    "      --index-pairs                           assign each of the two sample-barcode segments of the unmatched templates on its own\n"
+    "                                              (--max-mismatches and --min-mismatch-delta per index) against the sample sheet's distinct\n"
+    "                                              indexes, on the device, and write the pairs and their templates to <OUTPUT>/index-pairs.txt\n"
+    "                                              (index hopping, swapped plates); exactly two B segments of fixed length (additive flag)\n";
 
 bool parse_ulong(const std::string &s, unsigned long *out) {
     if (s.empty()) return false;
@@ -327,6 +333,7 @@ Options parse_args(int argc, char **argv) {
         else if (a == "--host-inflate") o.host_inflate = true;
         else if (a == "--gpu-gunzip") o.gpu_gunzip = true;
         else if (a == "--top-unmatched") num(&o.top_unmatched);
+        else if (a == "--index-pairs") o.index_pairs = true;
         else if (a == "--quality-metrics") o.quality_metrics = true;
         else if (a == "--help" || a == "-h") { std::fputs(kUsage, stdout); std::exit(0); }
         else die("unexpected argument '" + a + "' found\n\n" + kUsage);
@@ -602,6 +609,70 @@ void write_top_unmatched(const Options &opt, const std::vector<fqtk_matcher *> &
          (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3], rows.size(), path.c_str());
 }
 
+// --index-pairs: the same two steps for the index-pair tally (fqtk_matcher_pairs_*).  Rows: the non-zero cells summed over the
+// devices, templates descending, then index_1, then index_2 (bytewise; an unassigned index is `*`); then `skipped`.
+void enable_pairs(fqtk_matcher *m, const Options &opt) {
+    if (opt.index_pairs && fqtk_matcher_pairs_enable(m, opt.pairs_len_a, (uint32_t)opt.max_mismatches, (uint32_t)opt.min_mismatch_delta) != FQTK_OK)
+        die(std::string("cannot set up the index-pair tally: ") + fqtk_last_error());
+}
+
+void write_index_pairs(const Options &opt, const std::vector<fqtk_matcher *> &matchers, const std::vector<Sample> &samples) {
+    if (!opt.index_pairs) return;
+    uint32_t ua = 0, ub = 0;
+    if (fqtk_matcher_pairs_dims(matchers[0], &ua, &ub) != FQTK_OK) die(fqtk_last_error());
+    std::vector<std::string> index[2];
+    for (int w = 0; w < 2; ++w)
+        for (uint32_t i = 0; i < (w ? ub : ua); ++i) {
+            char buf[64];
+            if (fqtk_matcher_pairs_index(matchers[0], w, i, buf) != FQTK_OK) die(fqtk_last_error());
+            index[w].push_back(buf);
+        }
+    index[0].push_back("*");
+    index[1].push_back("*");
+    std::vector<uint64_t> sum((size_t)(ua + 1) * (ub + 1), 0), one(sum.size());
+    uint64_t skipped = 0;
+    for (fqtk_matcher *m : matchers) {   // every device's table is the same table: the same A and B
+        uint64_t sk = 0;
+        if (fqtk_matcher_pairs_read(m, one.data(), &sk) != FQTK_OK) die(fqtk_last_error());
+        for (size_t c = 0; c < sum.size(); ++c) sum[c] += one[c];
+        skipped += sk;
+    }
+    std::map<std::string, std::string> id_of;   // upper-cased barcode -> sample id
+    for (const Sample &s : samples) {
+        std::string b = s.barcode;
+        for (char &c : b) c = (char)std::toupper((unsigned char)c);
+        id_of.emplace(b, s.sample_id);
+    }
+    struct Row { uint64_t n; uint32_t a, b; };
+    std::vector<Row> rows;
+    uint64_t tallied = 0;
+    for (uint32_t a = 0; a <= ua; ++a)
+        for (uint32_t b = 0; b <= ub; ++b)
+            if (const uint64_t n = sum[(size_t)a * (ub + 1) + b]) { rows.push_back({n, a, b}); tallied += n; }
+    std::sort(rows.begin(), rows.end(), [&](const Row &x, const Row &y) {
+        if (x.n != y.n) return x.n > y.n;
+        if (index[0][x.a] != index[0][y.a]) return index[0][x.a] < index[0][y.a];
+        return index[1][x.b] < index[1][y.b];
+    });
+    std::string text = "index_1\tindex_2\ttemplates\tsample_id\n";
+    for (const Row &r : rows) {
+        const auto it = r.a < ua && r.b < ub ? id_of.find(index[0][r.a] + index[1][r.b]) : id_of.end();
+        text += index[0][r.a] + "\t" + index[1][r.b] + "\t" + std::to_string(r.n) + "\t" + (it == id_of.end() ? std::string("-") : it->second) + "\n";
+    }
+    text += "*\t*\t" + std::to_string(skipped) + "\tskipped\n";
+    const std::string path = opt.output + "/index-pairs.txt";
+    {
+        std::lock_guard<std::mutex> lk(g_created_mu);
+        g_created.push_back(path);
+    }
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) die("cannot create " + path + ": " + std::strerror(errno));
+    write_all(fd, reinterpret_cast<const uint8_t *>(text.data()), text.size(), path);
+    if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
+    info("Index pairs of the unmatched templates: %llu tallied over %zu pairs, %llu skipped (not of the barcodes' length); %s.",
+         (unsigned long long)tallied, rows.size(), (unsigned long long)skipped, path.c_str());
+}
+
 // --quality-metrics: the table (summed over devices, or over the router threads) as demux-quality-metrics.txt
 void write_quality_metrics(const Options &opt, const Plan &plan, const std::vector<Sample> &samples, const QualityTable &table) {
     std::vector<std::string> ids, barcodes;
@@ -725,6 +796,7 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
                 die(std::string("cannot create the GPU barcode matcher: ") + fqtk_last_error());
             fqtk_matcher_set_sample_ids(matchers[g], ids.data());
             enable_census(matchers[g], opt);
+            enable_pairs(matchers[g], opt);
             if (g_timing) info("(timing) matcher on device %d created; anonymous resident memory %zu MB.", opt.devices[g], rss_anon_mb());
             fqtk_demux_config cfg;
             std::memset(&cfg, 0, sizeof cfg);
@@ -1576,6 +1648,7 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
     rows.push_back(unmatched);
     std::string err;
     write_top_unmatched(opt, matchers, L);
+    write_index_pairs(opt, matchers, samples);
     if (opt.quality_metrics) {   // the devices' tables, summed (fqtk_demuxer_quality ADDS)
         QualityTable qt;
         qt.init(S, n_inputs);
@@ -1667,6 +1740,16 @@ int main(int argc, char **argv) {
         if (load_samples(opt.sample_metadata, &sheet, &err) && !sheet.empty() && sheet[0].barcode.size() > 32)
             die("invalid value for '--top-unmatched': the census of unmatched barcodes takes sample barcodes of at most 32 bases, those of \"" +
                 opt.sample_metadata + "\" have " + std::to_string(sheet[0].barcode.size()));
+    }
+    if (opt.index_pairs) {   // two indexes, each of a known length: said here, before any input is opened
+        std::vector<int> lens;
+        for (const ReadStructure &r : plan.rs)
+            for (const ReadSegment &seg : r.segments)
+                if (seg.kind == SegType::SampleBarcode) lens.push_back(seg.has_length() ? (int)seg.length : -1);
+        if (lens.size() != 2 || lens[0] < 0 || lens[1] < 0)
+            die("invalid use of '--index-pairs': the index-pair tally takes exactly two sample-barcode (B) segments of fixed length over all read "
+                "structures, these have " + std::to_string(lens.size()) + (lens.size() == 2 ? ", one of them of variable length" : ""));
+        opt.pairs_len_a = (uint32_t)lens[0];
     }
     std::vector<std::unique_ptr<FastqSource>> sources;
     // Single-stream gzip inputs are decoded by several threads each (parallel_gunzip.hpp): three quarters of the usable
@@ -1765,6 +1848,7 @@ int main(int argc, char **argv) {
             for (const Sample &s : samples) ids.push_back(s.sample_id.c_str());
             fqtk_matcher_set_sample_ids(matchers[g], ids.data());
             enable_census(matchers[g], opt);
+            enable_pairs(matchers[g], opt);
             info("GPU barcode matcher ready on device %d (%llu memo entries).", opt.devices[g],
                  (unsigned long long)fqtk_matcher_memo_entries(matchers[g]));
         }
@@ -2266,6 +2350,7 @@ int main(int argc, char **argv) {
     rows.push_back(unmatched);
     std::string err;
     write_top_unmatched(opt, matchers, L);
+    write_index_pairs(opt, matchers, samples);
     if (opt.quality_metrics) {
         for (size_t s = 0; s <= S; ++s)
             if (quality_total.row(s)[0] != counts[s]) die("internal error: the quality metrics' template counts differ from the per-sample counts");

@@ -263,6 +263,41 @@ int fqtk_matcher_census_totals(fqtk_matcher *m, uint64_t *distinct, uint64_t *ke
  * Only the `distinct` entries cross the link; the order is made on the host. */
 int fqtk_matcher_census_top(fqtk_matcher *m, uint32_t k, char *barcodes, uint64_t *counts, uint32_t *n_out);
 
+/* ---- index pairs of the unmatched reads: which index-1 x index-2 combinations did the None reads carry? ------------
+ * The index-hopping / swapped-plate / wrong-sample-sheet report of a dual-index run; no counterpart in the reference.
+ * Opt-in, owned by the handle, accumulated over every batch of every entry point like the census above, by one more kernel
+ * behind the batch's own on the batch's stream.  OFF (the default): no kernel is launched, no memory is taken and every
+ * result, count and error is what it is without these entry points.  With the census on as well, both run.
+ *   A, B     the distinct strings barcode_s[0 : len_a] and barcode_s[len_a : barcode_len] of the table (upper case, as the
+ *            matcher keeps it), each in order of first appearance; U_A and U_B of them.
+ *   assign   each index of a read is assigned on its own with the matcher's rule applied to that index's positions and that
+ *            list: mismatches counted as enc(read) & ~enc(index) != 0, best = the lowest count, idx = the lowest entry that has
+ *            it, next = the second smallest with multiplicity (255 for a list of one); unassigned when
+ *            best > max_mismatches or next - best < min_mismatch_delta (the two parameters given here, per index).
+ *            No special cases: N, lower case, '.', IUPAC codes and bytes that encode to 0 count as they do in the whole rule.
+ *   tallied  every None read of exactly barcode_len bases (stride >= barcode_len, and no obs_len or obs_len[i] ==
+ *            barcode_len) adds 1 to cell [a][b] of a (U_A + 1) x (U_B + 1) matrix of 64-bit counters; row U_A and column
+ *            U_B mean "this index unassigned".  A cell whose pair is a sample's own barcode is legal (one error in each index
+ *            with max_mismatches 1, say) and is reported.
+ *   skipped  every other None read adds 1 to one counter.
+ * At any quiescent point   sum(matrix) + skipped == number of None results produced since enable / reset.
+ * Device memory: 8 bytes a cell and 16 bytes per distinct index.
+ *
+ * enable: builds A, B and their planes, allocates and clears the matrix (again: with the new parameters, cleared).
+ * FQTK_EINVAL when barcode_len > 32, when len_a == 0 or len_a >= barcode_len, or when the matrix would have more than 2^24
+ * cells (128 MiB); FQTK_ENOMEM.  disable frees everything (fqtk_matcher_destroy does, too); reset clears the matrix and
+ * `skipped`.  All three wait for the device to drain first. */
+int fqtk_matcher_pairs_enable(fqtk_matcher *m, uint32_t len_a, uint32_t max_mismatches, uint32_t min_mismatch_delta);
+int fqtk_matcher_pairs_disable(fqtk_matcher *m);
+int fqtk_matcher_pairs_reset(fqtk_matcher *m);
+/* The read-outs return FQTK_EINVAL ("the index-pair tally is not enabled") when it is off.  dims: U_A and U_B.  index: entry i
+ * of A (which = 0) or B (which = 1) as a NUL-terminated string; out has room for barcode_len bytes.  read: synchronises the
+ * device and copies the matrix, row-major with (U_A + 1) * (U_B + 1) cells, and `skipped`; either pointer may be NULL; the
+ * tally stays as it is. */
+int fqtk_matcher_pairs_dims(fqtk_matcher *m, uint32_t *u_a, uint32_t *u_b);
+int fqtk_matcher_pairs_index(fqtk_matcher *m, int which, uint32_t i, char *out);
+int fqtk_matcher_pairs_read(fqtk_matcher *m, uint64_t *matrix, uint64_t *skipped);
+
 /* ---- several GPUs in one process------------------------------------------------ */
 /* Templates are independent, so chunks shard over devices with no data-path exchange: one matcher per
  * device (the table is replicated by fqtk_matcher_create), chunk k goes to matcher k mod n.  The ONE
