@@ -142,6 +142,11 @@ SIGNATURES = [
     ("fqtk_matcher_pairs_dims", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fqtk_matcher_pairs_index", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_char_p]),
     ("fqtk_matcher_pairs_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("fqtk_matcher_set_weighted", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("fqtk_matcher_assign_weighted_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+    ("fqtk_matcher_assign_weighted_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fqtk_matchers_allreduce_counts", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
     # include/fqtk_bgzf.h
     ("fqtk_bgzf_last_error", C.c_char_p, []),
@@ -166,6 +171,7 @@ SIGNATURES = [
     ("fqtk_demuxer_record_text", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     ("fqtk_demuxer_flush", C.c_int, [C.c_void_p, C.POINTER(fqtk_demux_result)]),
     ("fqtk_demuxer_counts", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fqtk_demuxer_weighted_enable", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     ("fqtk_demuxer_quality_enable", C.c_int, [C.c_void_p]),
     ("fqtk_demuxer_quality_row_words", C.c_uint32, [C.c_void_p]),
     ("fqtk_demuxer_quality", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -217,6 +217,33 @@ class BarcodeMatcher:
         _check(self._lib.fqtk_matcher_assign_batch_device(self._h, d_obs, stride, d_lens or None, n,
                                                           d_out, d_counts or None, stream or None))
 
+    # ---- quality-weighted assignment (fqtk_matcher_set_weighted / fqtk_matcher_assign_weighted_batch*) ---------------
+    def set_weighted(self, max_cost: int, min_cost_delta: int) -> None:
+        """Turns the weighted calls on: a mismatch at base i costs clamp(qual[i] - 33, 0, 93); None iff best > max_cost or
+        next - best < min_cost_delta.  ValueError for barcodes of more than 32 bases or more than 16384 samples."""
+        _check(self._lib.fqtk_matcher_set_weighted(self._h, int(max_cost), int(min_cost_delta)))
+
+    def assign_batch_weighted(self, obs: np.ndarray, qual: np.ndarray, max_cost: int, min_cost_delta: int, counts: bool = True):
+        """obs, qual: uint8 [n, stride] (host), every read barcode_len bases.  Returns (matches[MATCH_DTYPE n] with the costs
+        saturated at 255, costs uint32[n] = best | next << 16 or 0xFFFFFFFF for None, counts u64[S+1] or None)."""
+        obs = np.ascontiguousarray(obs, dtype=np.uint8)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8)
+        assert obs.ndim == 2 and qual.shape == obs.shape
+        n, stride = obs.shape
+        self.set_weighted(max_cost, min_cost_delta)
+        out = np.empty(n, dtype=MATCH_DTYPE)
+        costs = np.empty(n, dtype=np.uint32)
+        cnt = np.zeros(self.n_samples + 1, dtype=np.uint64) if counts else None
+        _check(self._lib.fqtk_matcher_assign_weighted_batch(self._h, obs.ctypes.data, qual.ctypes.data, stride, n, out.ctypes.data,
+                                                            costs.ctypes.data, cnt.ctypes.data if counts else None))
+        return out, costs, cnt
+
+    def assign_batch_weighted_device(self, d_obs: int, d_qual: int, stride: int, n: int, d_out: int, d_costs: int = 0,
+                                     d_counts: int = 0, stream: int = 0) -> None:
+        """Zero-copy form of the weighted call (after set_weighted): raw device pointers and a hipStream_t handle.  Asynchronous."""
+        _check(self._lib.fqtk_matcher_assign_weighted_batch_device(self._h, d_obs or None, d_qual or None, stride, n, d_out or None,
+                                                                   d_costs or None, d_counts or None, stream or None))
+
     # ---- census of the unmatched barcodes (fqtk_matcher_census_*) -----------------------------------------------
     def enable_census(self, capacity: int = 0) -> None:
         """From here on every None read of every batch is tallied on the device by its barcode (0: 2^20 table slots)."""

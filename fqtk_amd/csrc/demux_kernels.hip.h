@@ -335,6 +335,28 @@ __global__ __launch_bounds__(256) void k_extract(TextSet T, DevConfig C, uint32_
     if (lens) lens[t] = skip[t] ? 0u : bc_len[t];
 }
 
+// The quality bytes of the same spans, one row of `stride` bytes per template beside its barcode row (quality-weighted
+// assignment: fqtk_demuxer_weighted_enable; fixed-length B segments only, so every row holds barcode_len bytes).  A quality
+// line has its sequence's length (k_records reports a record whose has not), so the spans are the sequence's own.
+__global__ __launch_bounds__(256) void k_extract_qual(TextSet T, DevConfig C, uint32_t n, uint32_t stride, const uint8_t *skip, uint8_t *qual,
+                                                      const ChunkStatus *st) {
+    if (no_records(st)) return;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n) return;
+    uint8_t *row = qual + (size_t)t * stride;
+    uint32_t w = 0;
+    if (!skip[t])
+        for (uint32_t b = 0; b < C.n_b; ++b) {
+            const RecView r = T.rec[C.bseg[b].input][t];
+            uint32_t lo, hi;
+            fmt::segment_span(C.bseg[b].offset, C.bseg[b].length, r.seq_len, &lo, &hi);
+            const uint8_t *src = T.text[C.bseg[b].input] + r.qual_off;
+            const uint32_t room = T.len[C.bseg[b].input] - min(r.qual_off, T.len[C.bseg[b].input]);   // never past the text
+            for (uint32_t k = lo; k < hi && k < room && w < stride; ++k) row[w++] = src[k];
+        }
+    for (uint32_t k = w; k < stride; ++k) row[k] = 0;
+}
+
 // ---- placement ----------------------------------------------------------------------------------------------------------
 // Every output file is a byte stream in input order (the reference writes templates one after another).  A template's
 // record lands at (bytes of earlier templates of the same sample) in each of that sample's files: a prefix sum keyed by

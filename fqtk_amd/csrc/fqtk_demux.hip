@@ -81,7 +81,7 @@ struct Slot {
     DevBuf<uint8_t> text[FQTK_DEMUX_MAX_INPUTS];
     DevBuf<uint32_t> tile_cnt[FQTK_DEMUX_MAX_INPUTS], ls[FQTK_DEMUX_MAX_INPUTS];
     DevBuf<RecView> rec[FQTK_DEMUX_MAX_INPUTS];
-    DevBuf<uint8_t> skip, obs, slabs, out_slabs, packed;
+    DevBuf<uint8_t> skip, obs, bq, slabs, out_slabs, packed;   // (bq: the barcodes' quality rows, weighted assignment only)
     DevBuf<uint32_t> bc_len, lens, res, rec_off, tile_tot, chunk_tot, blk_file, out_len, crc;
     DevBuf<TemplatePlan> plans;
     DevBuf<FileChunk> fc;
@@ -200,6 +200,7 @@ struct fqtk_demuxer {
     QualConfig Q{};
     unsigned long long *d_qual = nullptr;   // [n_samples + 1][Q.row_words]
     uint32_t qual_grid = 0;                 // FQTK_QUALITY_GRID=k (tests, A/B runs): at most k workgroups, so that a small chunk takes many rounds
+    bool weighted = false;                  // quality-weighted assignment (fqtk_demuxer_weighted_enable)
     std::vector<fqtk_demux_segment> t_segs; // the T segments of all inputs as configured, in input order, wanted as files or not
     std::vector<uint32_t> t_seg_input;      // ... and whose each is
 };
@@ -439,7 +440,7 @@ void fqtk_demuxer_destroy(fqtk_demuxer *d) {
     for (Slot &s : d->slots) {
         for (int i = 0; i < FQTK_DEMUX_MAX_INPUTS; ++i) { s.text[i].release(); s.tile_cnt[i].release(); s.ls[i].release(); s.rec[i].release(); }
         s.skip.release(); s.obs.release(); s.slabs.release(); s.out_slabs.release(); s.packed.release();
-        s.bc_len.release(); s.lens.release(); s.res.release(); s.rec_off.release(); s.tile_tot.release(); s.chunk_tot.release();
+        s.bq.release(); s.bc_len.release(); s.lens.release(); s.res.release(); s.rec_off.release(); s.tile_tot.release(); s.chunk_tot.release();
         s.blk_file.release(); s.out_len.release(); s.crc.release(); s.plans.release(); s.fc.release(); s.desc.release();
         s.pos.release(); s.file_off.release(); s.h_file_off.release(); s.h_packed.release();
         if (s.d_status) (void)hipFree(s.d_status);
@@ -588,7 +589,12 @@ static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, 
     hipLaunchKernelGGL(k_extract, dim3(g256), dim3(256), 0, A, T, C, n, stride, s.skip.p, s.bc_len.p, s.obs.p, C.use_lens ? s.lens.p : (uint32_t *)nullptr, s.d_status);
     DX_TRY(hipGetLastError());
     DX_TRY(hipEventRecord(s.ev[1], A));
-    if ((rc = fqtk_matcher_assign_batch_device(d->m, s.obs.p, stride, C.use_lens ? s.lens.p : nullptr, n, s.res.p, nullptr, A)) != FQTK_OK) return rc;
+    if (d->weighted) {   // the qualities of the same spans, then the weighted scan (every row holds barcode_len bytes: no lens)
+        if ((rc = s.bq.ensure((size_t)n * stride + 64)) != FQTK_OK) return rc;
+        hipLaunchKernelGGL(k_extract_qual, dim3(g256), dim3(256), 0, A, T, C, n, stride, s.skip.p, s.bq.p, s.d_status);
+        DX_TRY(hipGetLastError());
+        if ((rc = fqtk_matcher_assign_weighted_batch_device(d->m, s.obs.p, s.bq.p, stride, n, s.res.p, nullptr, nullptr, A)) != FQTK_OK) return rc;
+    } else if ((rc = fqtk_matcher_assign_batch_device(d->m, s.obs.p, stride, C.use_lens ? s.lens.p : nullptr, n, s.res.p, nullptr, A)) != FQTK_OK) return rc;
     if ((rc = fqtk::internal::take_device_error(d->m, A, &s.d_status->matcher_err)) != FQTK_OK) return rc;
     DX_TRY(hipEventRecord(s.ev[2], A));
     DX_TRY(hipMemsetAsync(s.tile_tot.p, 0, (size_t)n_tiles * d->cols * sizeof(uint32_t), A));
@@ -1443,9 +1449,22 @@ int fqtk_demuxer_counts(fqtk_demuxer *d, uint64_t *counts) {
     return FQTK_OK;
 }
 
+int fqtk_demuxer_weighted_enable(fqtk_demuxer *d, uint32_t max_cost, uint32_t min_cost_delta) {
+    if (!d) return set_error(FQTK_EINVAL, "NULL argument");
+    if (d->chunk_no) return set_error(FQTK_EINVAL, "quality-weighted assignment is enabled before the first chunk is submitted");
+    if (d->C.variable_bc || d->C.fixed_bc_len != d->C.barcode_len)
+        return set_error(FQTK_EINVAL, "quality-weighted assignment takes sample-barcode (B) segments of fixed length that add up to the barcodes' length");
+    if (d->quality) return set_error(FQTK_EINVAL, "quality-weighted assignment and the quality tally do not combine: its match columns read a saturated cost");
+    const int rc = fqtk_matcher_set_weighted(d->m, max_cost, min_cost_delta);   // (its message stands)
+    if (rc != FQTK_OK) return rc;
+    d->weighted = true;
+    return FQTK_OK;
+}
+
 int fqtk_demuxer_quality_enable(fqtk_demuxer *d) {
     if (!d) return set_error(FQTK_EINVAL, "NULL argument");
     if (d->quality) return FQTK_OK;
+    if (d->weighted) return set_error(FQTK_EINVAL, "quality-weighted assignment and the quality tally do not combine: its match columns read a saturated cost");
     if (d->chunk_no) return set_error(FQTK_EINVAL, "the quality tally is enabled before the first chunk is submitted");
     if (d->t_segs.size() > kQualMaxSegs) return set_error(FQTK_EINVAL, "the quality tally takes at most 32 template segments over all inputs");
     QualConfig &Q = d->Q;

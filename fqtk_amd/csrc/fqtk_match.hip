@@ -37,6 +37,7 @@ extern "C" int fqtk_dev_phase_cycles(unsigned long long *out16) {
 #include "lds_memo_plan.hpp"
 #include "direct_memo_plan.hpp"
 #include "mfma_scan_kernels.hip.h"
+#include "weighted_scan_kernels.hip.h"
 #include "census_kernels.hip.h"
 #include "pair_kernels.hip.h"
 
@@ -125,6 +126,10 @@ struct Slot {
     size_t exc_index_cap = 0;
     uint8_t *d_exc_rows = nullptr;
     size_t exc_rows_cap = 0;
+    uint8_t *d_qual = nullptr;       // fqtk_matcher_assign_weighted_batch: the quality rows and the costs
+    size_t qual_cap = 0;
+    uint32_t *d_costs = nullptr;
+    size_t costs_cap = 0;            // elements
     bool busy = false;
     ErrCtx ctx;          // the chunk in flight on this slot
     Worklist work;
@@ -191,6 +196,9 @@ struct fqtk_matcher {
     uint8_t *d_mfma_rows = nullptr;            // sample operand, [ntiles * 32][rs]
     fqtk::MfmaScanPlan mfma{};
     int scan_kind_wanted = -1;                 // -1 = auto, else FQTK_SCAN_VALU / FQTK_SCAN_MFMA (FQTK_SCAN, set_scan_kind)
+    // quality-weighted assignment (weighted_scan_kernels.hip.h): its own entry points, on d_mfma_rows; off until set_weighted
+    bool weighted = false;
+    uint32_t max_cost = 0, min_cost_delta = 0;
     fqtk::Census census;                       // opt-in table of the unmatched barcodes (census_kernels.hip.h); off: nothing allocated
     fqtk::Pairs pairs;                         // opt-in index-pair tally of the unmatched reads (pair_kernels.hip.h); off: nothing allocated
     Slot slots[kNumSlots];
@@ -328,6 +336,73 @@ int launch_mfma_scan(const fqtk_matcher *m, const fqtk::MatchParams &P, hipStrea
         case 4: return launch_mfma_vec<4, 0, 1>(m, Q, stream);
         default: return fail(FQTK_EINVAL, "unsupported barcode length");
     }
+}
+
+// ---- quality-weighted assignment (weighted_scan_kernels.hip.h) -----------------------------------------------------------
+template <int KB, int VEC>
+int launch_weighted_t(const fqtk_matcher *m, const fqtk::WeightedScanParams &W, hipStream_t stream) {
+    const fqtk::MfmaScanPlan &pl = m->mfma;
+    const uint64_t tile = (uint64_t)(pl.block / 64) * 64;
+    const uint64_t ntiles = (W.q.m.n + tile - 1) / tile;
+    if (ntiles == 0) return FQTK_OK;
+    // persistent grid, sized as launch_mfma_t sizes it: the two kernels share plan, LDS carve-up and register bound
+    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(fqtk::kMfmaLdsBudget / pl.lds, fqtk::mfma_block_cap(KB) / pl.block));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->num_cus * per_cu);
+    auto kern = fqtk::weighted_scan_kernel<KB, VEC>;
+    const void *fn = reinterpret_cast<const void *>(kern);
+    if (pl.lds > 64 * 1024 && std::find(m->ldsm_big_lds_ok.begin(), m->ldsm_big_lds_ok.end(), fn) == m->ldsm_big_lds_ok.end()) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fqtk::kMfmaLdsBudget));
+        m->ldsm_big_lds_ok.push_back(fn);
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(pl.block), pl.lds, stream, W);
+    HIP_TRY(hipGetLastError());
+    return FQTK_OK;
+}
+
+// The load paths of launch_mfma_vec; one path serves both rows, so both bases decide it.
+template <int KB>
+int launch_weighted_vec(const fqtk_matcher *m, const fqtk::WeightedScanParams &W, hipStream_t stream) {
+    const fqtk::MatchParams &P = W.q.m;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(P.obs) | reinterpret_cast<uintptr_t>(W.qual);
+    const uint32_t nwords = (P.L + 3) / 4;
+    if (P.stride % 4 == 0 && base % 4 == 0 && P.stride >= nwords * 4) {
+        if constexpr (KB == 3) {
+            const uint32_t sw = P.stride / 4;
+            if (sw == nwords) {
+                if (sw == 4 && base % 16 == 0) return launch_weighted_t<KB, 4>(m, W, stream);
+                if (sw == 2 && base % 8 == 0) return launch_weighted_t<KB, 2>(m, W, stream);
+                if (sw == 1) return launch_weighted_t<KB, 1>(m, W, stream);
+                if (sw == 3) return launch_weighted_t<KB, 3>(m, W, stream);
+            }
+        }
+        return launch_weighted_t<KB, -1>(m, W, stream);
+    }
+    return launch_weighted_t<KB, 0>(m, W, stream);
+}
+
+// A weighted batch: weighted_scan_kernel and, when they are on, the census and the pair tally behind it, as launch() has them.
+int launch_weighted(const fqtk_matcher *m, const fqtk::MatchParams &P, const void *d_qual, void *d_costs, hipStream_t stream) {
+    const fqtk::MfmaScanPlan &pl = m->mfma;
+    fqtk::WeightedScanParams W;
+    W.q.m = P;
+    W.q.rows = m->d_mfma_rows;
+    W.q.lq = pl.lq;
+    W.q.ks = pl.ks;
+    W.q.rs = pl.rs;
+    W.q.ntiles = pl.ntiles;
+    // a staging of whole groups of four tiles, so that no chunk edge cuts a group (the kernel is right either way)
+    W.q.chunk_tiles = (pl.chunk_tiles < pl.ntiles && pl.chunk_tiles >= 4) ? (pl.chunk_tiles & ~3u) : pl.chunk_tiles;
+    W.qual = static_cast<const uint8_t *>(d_qual);
+    W.costs = static_cast<uint32_t *>(d_costs);
+    W.max_cost = m->max_cost;
+    W.min_cost_delta = m->min_cost_delta;
+    const int rc = pl.kb == 3 ? launch_weighted_vec<3>(m, W, stream) : launch_weighted_vec<6>(m, W, stream);
+    if (rc != FQTK_OK || !(m->census.on() || m->pairs.on())) return rc;
+    if (m->census.on()) {
+        const int rc_census = fqtk::census_launch(m->census, P, m->num_cus, stream);
+        if (rc_census != FQTK_OK) return rc_census;
+    }
+    return m->pairs.on() ? fqtk::pairs_launch(m->pairs, P, m->num_cus, stream) : FQTK_OK;
 }
 
 // The sample operand of the MFMA scan (layout: mfma_scan_kernels.hip.h), built once per matcher.  Not eligible
@@ -1549,6 +1624,8 @@ void fqtk_matcher_destroy(fqtk_matcher *m) {
         if (s.d_packed) (void)hipFree(s.d_packed);
         if (s.d_exc_index) (void)hipFree(s.d_exc_index);
         if (s.d_exc_rows) (void)hipFree(s.d_exc_rows);
+        if (s.d_qual) (void)hipFree(s.d_qual);
+        if (s.d_costs) (void)hipFree(s.d_costs);
         s.work.release();
     }
     if (m->d_memo) (void)hipFree(m->d_memo);
@@ -1706,6 +1783,76 @@ int fqtk_matcher_assign_batch_device(fqtk_matcher *m, const void *d_obs, uint32_
     Worklist *wl = nullptr;
     if ((rc = worklist_of_stream(m, static_cast<hipStream_t>(hip_stream), &wl)) != FQTK_OK) return rc;
     return launch(m, P, static_cast<hipStream_t>(hip_stream), *wl);
+}
+
+// ---- quality-weighted assignment (weighted_scan_kernels.hip.h) -----------------------------------------------------------
+int fqtk_matcher_set_weighted(fqtk_matcher *m, uint32_t max_cost, uint32_t min_cost_delta) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    if (m->L > fqtk::kWeightedMaxLen)
+        return fail(FQTK_EINVAL, "quality-weighted assignment serves barcodes of at most 32 bases; these have " + std::to_string(m->L));
+    if (m->S > fqtk::kMfmaMaxSamples)
+        return fail(FQTK_EINVAL, "quality-weighted assignment serves at most 16384 samples; this table has " + std::to_string(m->S));
+    if (!m->d_mfma_rows || !m->mfma.kb) return fail(FQTK_EINVAL, "quality-weighted assignment: this table has no sample operand rows");
+    m->max_cost = max_cost;
+    m->min_cost_delta = min_cost_delta;
+    m->weighted = true;
+    return FQTK_OK;
+}
+
+static int check_weighted_args(const fqtk_matcher *m, const void *obs, const void *qual, uint32_t stride, uint64_t n, const void *out) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    if (!m->weighted) return fail(FQTK_EINVAL, "quality-weighted assignment is not set up: call fqtk_matcher_set_weighted() first");
+    if (n == 0) return FQTK_OK;
+    if (!obs || !out) return fail(FQTK_EINVAL, "obs/out is NULL");
+    if (!qual) return fail(FQTK_EINVAL, "qual is NULL");
+    if (stride < m->L) return fail(FQTK_EINVAL, "stride < barcode_len: quality-weighted assignment has no obs_len form");
+    return FQTK_OK;
+}
+
+int fqtk_matcher_assign_weighted_batch_device(fqtk_matcher *m, const void *d_obs, const void *d_qual, uint32_t stride, uint64_t n,
+                                              void *d_out, void *d_costs, void *d_counts, void *hip_stream) {
+    const int rc = check_weighted_args(m, d_obs, d_qual, stride, n, d_out);
+    if (rc != FQTK_OK || n == 0) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    const fqtk::MatchParams P = make_params(m, d_obs, stride, nullptr, n, d_out, d_counts, kDeviceErrWord);
+    return launch_weighted(m, P, d_qual, d_costs, static_cast<hipStream_t>(hip_stream));
+}
+
+int fqtk_matcher_assign_weighted_batch(fqtk_matcher *m, const uint8_t *obs, const uint8_t *qual, uint32_t stride, uint64_t n,
+                                       fqtk_match_t *out, uint32_t *costs, uint64_t *counts) {
+    int rc = check_weighted_args(m, obs, qual, stride, n, out);
+    if (rc != FQTK_OK || n == 0) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    if ((rc = ensure_slot(m, kSyncSlot0)) != FQTK_OK) return rc;
+    Slot &s = m->slots[kSyncSlot0];   // private to the synchronous calls; one chunk at a time
+    if (s.busy) return fail(FQTK_EINVAL, "slot is busy");
+    const size_t bins = (size_t)m->S + 1;
+    if (counts) {
+        HIP_TRY(hipMemset(m->d_counts_sync, 0, bins * sizeof(unsigned long long)));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // must land before the kernels on the non-blocking slot stream
+    }
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, (256ull << 20) / stride));
+    for (uint64_t done = 0; done < n; done += chunk) {
+        const uint64_t cur = std::min(chunk, n - done);
+        const size_t bytes = (size_t)cur * stride;
+        if ((rc = ensure_cap(s.d_obs, s.obs_cap, bytes + 16)) != FQTK_OK) return rc;
+        if ((rc = ensure_cap(s.d_qual, s.qual_cap, bytes + 16)) != FQTK_OK) return rc;
+        if ((rc = ensure_cap(s.d_out, s.out_cap, (size_t)cur)) != FQTK_OK) return rc;
+        if (costs && (rc = ensure_cap(s.d_costs, s.costs_cap, (size_t)cur)) != FQTK_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(s.d_obs, obs + done * stride, bytes, hipMemcpyHostToDevice, s.stream));
+        HIP_TRY(hipMemcpyAsync(s.d_qual, qual + done * stride, bytes, hipMemcpyHostToDevice, s.stream));
+        const fqtk::MatchParams P = make_params(m, s.d_obs, stride, nullptr, cur, s.d_out, counts ? m->d_counts_sync : nullptr, kSyncSlot0);
+        if ((rc = launch_weighted(m, P, s.d_qual, costs ? s.d_costs : nullptr, s.stream)) != FQTK_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(out + done, s.d_out, (size_t)cur * sizeof(fqtk_match_t), hipMemcpyDeviceToHost, s.stream));
+        if (costs) HIP_TRY(hipMemcpyAsync(costs + done, s.d_costs, (size_t)cur * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipStreamSynchronize(s.stream));
+    }
+    if (counts) {
+        std::vector<unsigned long long> tmp(bins);
+        HIP_TRY(hipMemcpy(tmp.data(), m->d_counts_sync, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < bins; ++b) counts[b] += (uint64_t)tmp[b];
+    }
+    return FQTK_OK;
 }
 
 int fqtk_matcher_poll_error(fqtk_matcher *m, void *hip_stream, uint64_t *read_index) {

@@ -202,6 +202,9 @@ struct Options {
     bool index_pairs = false;        // --index-pairs: index-1 x index-2 tally of the unmatched templates on the device -> index-pairs.txt
     uint32_t pairs_len_a = 0;        //   length of the first of the two sample-barcode segments (main() works it out before any input is opened)
     bool quality_metrics = false;    // --quality-metrics: per-sample yield and quality in demux-quality-metrics.txt
+    bool weighted = false;           // --quality-weighted MAXCOST,DELTA: a mismatch costs the base's quality (fqtk_demuxer_weighted_enable)
+    unsigned long max_cost = 0, min_cost_delta = 0;
+    bool mismatch_flags_given = false;   //   --max-mismatches / --min-mismatch-delta were given: ignored with --quality-weighted, and said so
 };
 
 const char *kUsage =
@@ -243,7 +246,12 @@ const char *kUsage =
     "      --index-pairs                           assign each of the two sample-barcode segments of the unmatched templates on its own\n"
     "                                              (--max-mismatches and --min-mismatch-delta per index) against the sample sheet's distinct\n"
     "                                              indexes, on the device, and write the pairs and their templates to <OUTPUT>/index-pairs.txt\n"
-    "                                              (index hopping, swapped plates); exactly two B segments of fixed length (additive flag)\n";
+    "                                              (index hopping, swapped plates); exactly two B segments of fixed length (additive flag)\n"
+    "      --quality-weighted <MAXCOST,DELTA>      assign by quality-weighted cost on the device: a mismatching base costs its Phred quality\n"
+    "                                              (quality byte - 33, clamped to 0..93); a template is unmatched when its best cost is above MAXCOST\n"
+    "                                              or the next best is less than DELTA away; --max-mismatches and --min-mismatch-delta are ignored;\n"
+    "                                              B segments of fixed length, at most 32 bases and 16384 samples; not with --host-output or\n"
+    "                                              --quality-metrics (additive flag)\n";
 
 bool parse_ulong(const std::string &s, unsigned long *out) {
     if (s.empty()) return false;
@@ -308,8 +316,16 @@ Options parse_args(int argc, char **argv) {
         } else if (a == "--sample-metadata") o.sample_metadata = single();
         else if (a == "--output") o.output = single();
         else if (a == "--unmatched-prefix") o.unmatched_prefix = single();
-        else if (a == "--max-mismatches") num(&o.max_mismatches);
-        else if (a == "--min-mismatch-delta") num(&o.min_mismatch_delta);
+        else if (a == "--max-mismatches") { num(&o.max_mismatches); o.mismatch_flags_given = true; }
+        else if (a == "--min-mismatch-delta") { num(&o.min_mismatch_delta); o.mismatch_flags_given = true; }
+        else if (a == "--quality-weighted") {
+            const std::string v = single();
+            const size_t q = v.find(',');
+            if (q == std::string::npos || !parse_ulong(v.substr(0, q), &o.max_cost) || !parse_ulong(v.substr(q + 1), &o.min_cost_delta) ||
+                o.max_cost > 0xFFFFFFFFul || o.min_cost_delta > 0xFFFFFFFFul)
+                die("invalid value '" + v + "' for '--quality-weighted': expected MAXCOST,DELTA (two non-negative integers)");
+            o.weighted = true;
+        }
         else if (a == "--threads") num(&o.threads);
         else if (a == "--compression-level") num(&o.compression_level);
         else if (a == "--skip-reasons") multi(o.skip_reasons);
@@ -810,6 +826,8 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
             cfg.compression_level = (int)opt.compression_level;
             if (fqtk_demuxer_create(matchers[g], &cfg, &demuxers[g]) != FQTK_OK) die(std::string("cannot set up the GPU record pipeline: ") + fqtk_last_error());
             if (opt.quality_metrics && fqtk_demuxer_quality_enable(demuxers[g]) != FQTK_OK) die(std::string("cannot set up the quality metrics: ") + fqtk_last_error());
+            if (opt.weighted && fqtk_demuxer_weighted_enable(demuxers[g], (uint32_t)opt.max_cost, (uint32_t)opt.min_cost_delta) != FQTK_OK)
+                die(std::string("cannot set up quality-weighted assignment: ") + fqtk_last_error());
             info("GPU barcode matcher and record pipeline ready on device %d (%llu memo entries).", opt.devices[g],
                  (unsigned long long)fqtk_matcher_memo_entries(matchers[g]));
             if (g_timing) info("(timing) anonymous resident memory: %zu MB.", rss_anon_mb());
@@ -1751,6 +1769,22 @@ int main(int argc, char **argv) {
                 "structures, these have " + std::to_string(lens.size()) + (lens.size() == 2 ? ", one of them of variable length" : ""));
         opt.pairs_len_a = (uint32_t)lens[0];
     }
+    if (opt.weighted) {   // what the weighted rule does not take: said here, before any input is opened
+        if (opt.host_output || env_on("FQTK_HOST_OUTPUT"))
+            die("invalid use of '--quality-weighted' with '--host-output': the host routers carry no quality rows of the sample barcodes; "
+                "quality-weighted assignment runs in the GPU record pipeline only");
+        for (const ReadStructure &r : plan.rs)
+            for (const ReadSegment &seg : r.segments)
+                if (seg.kind == SegType::SampleBarcode && !seg.has_length())
+                    die("invalid use of '--quality-weighted': a sample-barcode segment of variable length ('+B') is not taken; "
+                        "quality-weighted assignment needs every sample barcode to have the sample sheet's length");
+        if (opt.quality_metrics)
+            die("invalid use of '--quality-weighted' with '--quality-metrics': the perfect / one-mismatch columns of demux-quality-metrics.txt "
+                "read the match's mismatch count, which is a saturated cost under quality-weighted assignment");
+        if (opt.mismatch_flags_given)
+            std::fprintf(stderr, "Note: --max-mismatches and --min-mismatch-delta are ignored with --quality-weighted (MAXCOST %lu, DELTA %lu decide).\n",
+                         opt.max_cost, opt.min_cost_delta);
+    }
     std::vector<std::unique_ptr<FastqSource>> sources;
     // Single-stream gzip inputs are decoded by several threads each (parallel_gunzip.hpp): three quarters of the usable
     // CPUs, shared out by file size (the index reads of a run are a fifth of its bytes), at most 8 per file.
@@ -1834,6 +1868,8 @@ int main(int argc, char **argv) {
     if (!opt.host_output && !env_on("FQTK_HOST_OUTPUT")) {
         std::string why;
         if (gpu_output_supported(plan, &why)) run_gpu_output(opt, plan, samples, sources, skip_few);   // does not return
+        if (opt.weighted)
+            die("invalid use of '--quality-weighted': the GPU record pipeline does not take this configuration (" + why + "), and the host routers carry no quality rows");
         info("The GPU record pipeline does not take this configuration (%s): records are formatted and compressed on the host.", why.c_str());
     }
     const size_t G = opt.devices.size();

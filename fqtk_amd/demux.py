@@ -211,6 +211,10 @@ class Demuxer:
         _check(self._lib.fqtk_demuxer_counts(self._h, c.ctypes.data))
         return c
 
+    def enable_weighted(self, max_cost: int, min_cost_delta: int) -> None:
+        """Quality-weighted assignment of every chunk's templates from the next chunk on (before the first submit; fixed-length B segments)."""
+        _check(self._lib.fqtk_demuxer_weighted_enable(self._h, int(max_cost), int(min_cost_delta)))
+
     def enable_quality(self) -> None:
         """Per-sample yield and quality metrics are tallied on the device from the next chunk on (before the first submit)."""
         _check(self._lib.fqtk_demuxer_quality_enable(self._h))

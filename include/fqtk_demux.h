@@ -233,6 +233,16 @@ int fqtk_demuxer_flush(fqtk_demuxer *d, fqtk_demux_result *res);
 /* Adds the per-sample template counts (n_samples + 1, unmatched last) of all collected chunks into counts. */
 int fqtk_demuxer_counts(fqtk_demuxer *d, uint64_t *counts);
 
+/* ---- quality-weighted assignment of the chunks' templates (opt-in; the rule: fqtk_match.h, fqtk_matcher_set_weighted) ---------
+ * Once enabled, every chunk also extracts the quality bytes of its sample-barcode (B) spans into a second row per template and
+ * its match step is fqtk_matcher_assign_weighted_batch_device; the matcher's max_mismatches / min_mismatch_delta play no part.
+ * Everything behind the match step is unchanged (the `best` / `next` bytes of a result are costs saturated at 255).
+ * Before the first submit.  FQTK_EINVAL: after a submit; a variable-length '+B' segment, or B segments that do not add up to the
+ * barcodes' length (the weighted rule has no obs_len form); together with fqtk_demuxer_quality_enable, in either order (its
+ * perfect / one-mismatch columns read the `best` byte); barcodes over 32 bases or more than 16384 samples.
+ * Not enabled: no kernel runs, nothing is allocated. */
+int fqtk_demuxer_weighted_enable(fqtk_demuxer *d, uint32_t max_cost, uint32_t min_cost_delta);
+
 /* ---- per-sample yield and quality metrics, tallied on the device (opt-in) ---------------------------------------------------
  * Once enabled, every chunk adds one row of counters per sample (n_samples + 1 rows, unmatched last) for the templates it
  * does not drop:

@@ -298,6 +298,38 @@ int fqtk_matcher_pairs_dims(fqtk_matcher *m, uint32_t *u_a, uint32_t *u_b);
 int fqtk_matcher_pairs_index(fqtk_matcher *m, int which, uint32_t i, char *out);
 int fqtk_matcher_pairs_read(fqtk_matcher *m, uint64_t *matrix, uint64_t *skipped);
 
+/* ---- quality-weighted assignment: a mismatch costs what the sequencer said about that base ---------------------------
+ * No counterpart in the reference, whose rule counts every mismatch as 1.  Here (all integer):
+ *   w[i]    = clamp(qual[i] - 33, 0, 93)        every byte value is defined: below '!' is 0, above '~' is 93
+ *   cost[s] = sum over i < barcode_len of  w[i] * [ enc(read[i]) & ~enc(barcode_s[i]) != 0 ]      (enc as everywhere else)
+ *   best = the lowest cost, idx = the LOWEST s that has it, next = the second smallest with multiplicity (0xFFFF for a
+ *   table of one sample);   None  iff  best > max_cost  or  next - best < min_cost_delta.
+ * A read byte that enc() maps to 0 never mismatches; a no-call costs its own quality against every sample base that is not N.
+ * With every quality equal to q, cost = q * mismatches: max_cost = q * mm + q - 1 and min_cost_delta = q * delta make the
+ * decisions of max_mismatches = mm, min_mismatch_delta = delta.
+ * The answer depends on the qualities, so no memo serves it: every read takes the scan of weighted_scan_kernels.hip.h (int8
+ * matrix cores).  Scope: every read has exactly barcode_len bases (no obs_len form), barcode_len <= 32 (a cost is at most
+ * 32 * 93 = 2976), n_samples <= 16384.  The matcher's max_mismatches / min_mismatch_delta play no part in these calls, and
+ * these calls none in the others: set_weighted changes nothing for any other entry point.
+ *
+ * set_weighted: sets (or changes) the two bounds and turns the two calls below on.  FQTK_EINVAL for barcode_len > 32 or
+ * n_samples > 16384.
+ * assign_weighted_batch: host pointers, synchronous, on a pipeline slot of its own like fqtk_matcher_assign_batch.  obs and
+ * qual are n rows `stride` bytes apart each (stride >= barcode_len; what follows the barcode in a row is not looked at).
+ *   out[i]    idx, best = min(best cost, 255), next = min(next cost, 255); idx == FQTK_NO_MATCH (all bits set) for None
+ *   costs     NULL, or n words: best cost | next cost << 16, 0xFFFFFFFF for None
+ *   counts    NULL, or S+1 counters that are ADDED to, as for fqtk_matcher_assign_batch
+ * assign_weighted_batch_device: the same with DEVICE pointers, enqueued on `hip_stream` without synchronising; d_counts NULL
+ * or S+1 uint64 accumulated with atomics.  Nothing is latched: there is no length error to raise.
+ * FQTK_EINVAL: before set_weighted, qual (or obs, out) NULL, stride < barcode_len.
+ * With the census or the index-pair tally enabled they run behind a weighted batch as behind any other and see its None
+ * results; the pair tally keeps its own UNWEIGHTED per-index rule (fqtk_matcher_pairs_enable's two parameters). */
+int fqtk_matcher_set_weighted(fqtk_matcher *m, uint32_t max_cost, uint32_t min_cost_delta);
+int fqtk_matcher_assign_weighted_batch(fqtk_matcher *m, const uint8_t *obs, const uint8_t *qual, uint32_t stride, uint64_t n,
+                                       fqtk_match_t *out, uint32_t *costs, uint64_t *counts);
+int fqtk_matcher_assign_weighted_batch_device(fqtk_matcher *m, const void *d_obs, const void *d_qual, uint32_t stride, uint64_t n,
+                                              void *d_out, void *d_costs, void *d_counts, void *hip_stream);
+
 /* ---- several GPUs in one process------------------------------------------------ */
 /* Templates are independent, so chunks shard over devices with no data-path exchange: one matcher per
  * device (the table is replicated by fqtk_matcher_create), chunk k goes to matcher k mod n.  The ONE
