@@ -142,6 +142,10 @@ SIGNATURES = [
     ("fqtk_matcher_pairs_dims", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fqtk_matcher_pairs_index", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_char_p]),
     ("fqtk_matcher_pairs_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("fqtk_matcher_indel_enable", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("fqtk_matcher_indel_disable", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_indel_reset", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_indel_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("fqtk_matcher_set_weighted", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     ("fqtk_matcher_assign_weighted_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]),

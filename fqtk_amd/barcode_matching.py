@@ -305,6 +305,26 @@ class BarcodeMatcher:
         _check(self._lib.fqtk_matcher_pairs_read(self._h, mat.ctypes.data, C.byref(skipped)))
         return mat, int(skipped.value)
 
+    # ---- indel rescue of the unmatched reads (fqtk_matcher_indel_*) ----------------------------------------------
+    def enable_indel_rescue(self, max_edits: int, min_edit_delta: int) -> None:
+        """From here on every None read of barcode_len bases of every batch gets a second look under the sequence-Levenshtein
+        distance (substitutions, insertions, deletions); a rescued read has bit 7 of `best` set and its count moved."""
+        _check(self._lib.fqtk_matcher_indel_enable(self._h, int(max_edits), int(min_edit_delta)))
+
+    def disable_indel_rescue(self) -> None:
+        _check(self._lib.fqtk_matcher_indel_disable(self._h))
+
+    def reset_indel_rescue(self) -> None:
+        _check(self._lib.fqtk_matcher_indel_reset(self._h))
+
+    def indel_rescued(self) -> tuple:
+        """(rescued uint64 [S + 1], skipped): [s] = reads rescued into s, [S] = examined and left None; skipped = None reads of
+        another length."""
+        rescued = np.zeros(self.n_samples + 1, dtype=np.uint64)
+        skipped = C.c_uint64(0)
+        _check(self._lib.fqtk_matcher_indel_read(self._h, rescued.ctypes.data, C.byref(skipped)))
+        return rescued, int(skipped.value)
+
     def poll_error(self, stream: int = 0) -> None:
         idx = C.c_uint64(0)
         _check(self._lib.fqtk_matcher_poll_error(self._h, stream or None, C.byref(idx)))

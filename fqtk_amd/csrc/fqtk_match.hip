@@ -40,6 +40,7 @@ extern "C" int fqtk_dev_phase_cycles(unsigned long long *out16) {
 #include "weighted_scan_kernels.hip.h"
 #include "census_kernels.hip.h"
 #include "pair_kernels.hip.h"
+#include "indel_kernels.hip.h"
 
 namespace {
 
@@ -201,6 +202,7 @@ struct fqtk_matcher {
     uint32_t max_cost = 0, min_cost_delta = 0;
     fqtk::Census census;                       // opt-in table of the unmatched barcodes (census_kernels.hip.h); off: nothing allocated
     fqtk::Pairs pairs;                         // opt-in index-pair tally of the unmatched reads (pair_kernels.hip.h); off: nothing allocated
+    fqtk::Indel indel;                         // opt-in indel rescue of the unmatched reads (indel_kernels.hip.h); off: nothing allocated
     Slot slots[kNumSlots];
 };
 
@@ -865,10 +867,15 @@ int launch_match(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t
 }
 
 // Every entry point's batch goes through here: the matcher's kernels and, with the census on, census_kernel behind them on the
-// same stream (out[] is final there).  Census off: this one branch.
+// same stream (out[] is final there).  Census off: this one branch.  The indel rescue, when on, runs first of the three: it
+// changes results, and the two tallies are of the reads that remain None.
 int launch(const fqtk_matcher *m, const fqtk::MatchParams &P0, hipStream_t stream, Worklist &wl) {
     const int rc = launch_match(m, P0, stream, wl);
-    if (rc != FQTK_OK || !(m->census.on() || m->pairs.on())) return rc;
+    if (rc != FQTK_OK || !(m->census.on() || m->pairs.on() || m->indel.on())) return rc;
+    if (m->indel.on() && P0.stride >= P0.L) {   // shorter rows: every read is shorter than a barcode
+        const int rc_indel = fqtk::indel_launch(m->indel, P0, m->num_cus, stream);
+        if (rc_indel != FQTK_OK) return rc_indel;
+    }
     if (m->census.on()) {
         const int rc_census = fqtk::census_launch(m->census, P0, m->num_cus, stream);
         if (rc_census != FQTK_OK) return rc_census;
@@ -1638,6 +1645,7 @@ void fqtk_matcher_destroy(fqtk_matcher *m) {
     if (m->d_mfma_rows) (void)hipFree(m->d_mfma_rows);
     (void)fqtk::census_disable(m->census);
     (void)fqtk::pairs_disable(m->pairs);
+    (void)fqtk::indel_disable(m->indel);
     if (m->d_table) (void)hipFree(m->d_table);
     if (m->d_lut) (void)hipFree(m->d_lut);
     if (m->d_err) (void)hipFree(m->d_err);
@@ -1770,6 +1778,31 @@ int fqtk_matcher_pairs_read(fqtk_matcher *m, uint64_t *matrix, uint64_t *skipped
     if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
     HIP_TRY(hipSetDevice(m->device));
     return fqtk::pairs_read(m->pairs, matrix, skipped);
+}
+
+// ---- indel rescue of the unmatched reads (indel_kernels.hip.h) ---------------------------------------------------------
+int fqtk_matcher_indel_enable(fqtk_matcher *m, uint32_t max_edits, uint32_t min_edit_delta) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::indel_enable(m->indel, m->barcodes_upper, m->L, max_edits, min_edit_delta, enc_byte);
+}
+
+int fqtk_matcher_indel_disable(fqtk_matcher *m) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::indel_disable(m->indel);
+}
+
+int fqtk_matcher_indel_reset(fqtk_matcher *m) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::indel_reset(m->indel);
+}
+
+int fqtk_matcher_indel_read(fqtk_matcher *m, uint64_t *rescued, uint64_t *skipped) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    return fqtk::indel_read(m->indel, rescued, skipped);
 }
 
 int fqtk_matcher_assign_batch_device(fqtk_matcher *m, const void *d_obs, uint32_t stride,

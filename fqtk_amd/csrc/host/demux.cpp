@@ -205,6 +205,8 @@ struct Options {
     bool weighted = false;           // --quality-weighted MAXCOST,DELTA: a mismatch costs the base's quality (fqtk_demuxer_weighted_enable)
     unsigned long max_cost = 0, min_cost_delta = 0;
     bool mismatch_flags_given = false;   //   --max-mismatches / --min-mismatch-delta were given: ignored with --quality-weighted, and said so
+    bool indel_rescue = false;       // --indel-rescue MAXEDITS,DELTA: unmatched templates get a second look under an edit-distance rule on the device
+    unsigned long max_edits = 0, min_edit_delta = 0;
 };
 
 const char *kUsage =
@@ -251,7 +253,14 @@ const char *kUsage =
     "                                              (quality byte - 33, clamped to 0..93); a template is unmatched when its best cost is above MAXCOST\n"
     "                                              or the next best is less than DELTA away; --max-mismatches and --min-mismatch-delta are ignored;\n"
     "                                              B segments of fixed length, at most 32 bases and 16384 samples; not with --host-output or\n"
-    "                                              --quality-metrics (additive flag)\n";
+    "                                              --quality-metrics (additive flag)\n"
+    "      --indel-rescue <MAXEDITS,DELTA>         give the unmatched templates a second look on the device under the edit distance to every\n"
+    "                                              sample barcode (substitutions, one inserted or deleted base and what it shifts in or out):\n"
+    "                                              a template whose best distance is at most MAXEDITS and whose next best is at least DELTA\n"
+    "                                              away goes to that sample; the files, demux-metrics.txt and the other reports see the result,\n"
+    "                                              and <OUTPUT>/indel-rescue.txt has the rescued templates per sample; B segments of fixed length,\n"
+    "                                              at most 32 bases, MAXEDITS + DELTA from 1 to 16; works with --host-output too; not with\n"
+    "                                              --quality-weighted (additive flag)\n";
 
 bool parse_ulong(const std::string &s, unsigned long *out) {
     if (s.empty()) return false;
@@ -325,6 +334,14 @@ Options parse_args(int argc, char **argv) {
                 o.max_cost > 0xFFFFFFFFul || o.min_cost_delta > 0xFFFFFFFFul)
                 die("invalid value '" + v + "' for '--quality-weighted': expected MAXCOST,DELTA (two non-negative integers)");
             o.weighted = true;
+        }
+        else if (a == "--indel-rescue") {
+            const std::string v = single();
+            const size_t q = v.find(',');
+            if (q == std::string::npos || !parse_ulong(v.substr(0, q), &o.max_edits) || !parse_ulong(v.substr(q + 1), &o.min_edit_delta) ||
+                o.max_edits > 255 || o.min_edit_delta > 255)
+                die("invalid value '" + v + "' for '--indel-rescue': expected MAXEDITS,DELTA (two non-negative integers)");
+            o.indel_rescue = true;
         }
         else if (a == "--threads") num(&o.threads);
         else if (a == "--compression-level") num(&o.compression_level);
@@ -689,6 +706,44 @@ void write_index_pairs(const Options &opt, const std::vector<fqtk_matcher *> &ma
          (unsigned long long)tallied, rows.size(), (unsigned long long)skipped, path.c_str());
 }
 
+// --indel-rescue: the same two steps for the indel rescue (fqtk_matcher_indel_*).  Rows: per sample the templates rescued into it,
+// summed over the devices; then the templates examined and left unmatched; then those skipped (not of the barcodes' length).
+void enable_indel(fqtk_matcher *m, const Options &opt) {
+    if (opt.indel_rescue && fqtk_matcher_indel_enable(m, (uint32_t)opt.max_edits, (uint32_t)opt.min_edit_delta) != FQTK_OK)
+        die(std::string("cannot set up the indel rescue: ") + fqtk_last_error());
+}
+
+void write_indel_rescue(const Options &opt, const std::vector<fqtk_matcher *> &matchers, const std::vector<Sample> &samples) {
+    if (!opt.indel_rescue) return;
+    const size_t S = samples.size();
+    std::vector<uint64_t> sum(S + 1, 0), one(S + 1);
+    uint64_t skipped = 0, rescued = 0;
+    for (fqtk_matcher *m : matchers) {
+        uint64_t sk = 0;
+        if (fqtk_matcher_indel_read(m, one.data(), &sk) != FQTK_OK) die(fqtk_last_error());
+        for (size_t s = 0; s <= S; ++s) sum[s] += one[s];
+        skipped += sk;
+    }
+    std::string text = "sample_id\tbarcode\trescued_templates\n";
+    for (size_t s = 0; s < S; ++s) {
+        text += samples[s].sample_id + "\t" + samples[s].barcode + "\t" + std::to_string(sum[s]) + "\n";
+        rescued += sum[s];
+    }
+    text += opt.unmatched_prefix + "\t.\t" + std::to_string(sum[S]) + "\n";
+    text += "skipped\t.\t" + std::to_string(skipped) + "\n";
+    const std::string path = opt.output + "/indel-rescue.txt";
+    {
+        std::lock_guard<std::mutex> lk(g_created_mu);
+        g_created.push_back(path);
+    }
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) die("cannot create " + path + ": " + std::strerror(errno));
+    write_all(fd, reinterpret_cast<const uint8_t *>(text.data()), text.size(), path);
+    if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
+    info("Indel rescue (at most %lu edits, next best at least %lu away): %llu templates rescued, %llu examined and left unmatched, %llu skipped (not of the barcodes' length); %s.",
+         opt.max_edits, opt.min_edit_delta, (unsigned long long)rescued, (unsigned long long)sum[S], (unsigned long long)skipped, path.c_str());
+}
+
 // --quality-metrics: the table (summed over devices, or over the router threads) as demux-quality-metrics.txt
 void write_quality_metrics(const Options &opt, const Plan &plan, const std::vector<Sample> &samples, const QualityTable &table) {
     std::vector<std::string> ids, barcodes;
@@ -813,6 +868,7 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
             fqtk_matcher_set_sample_ids(matchers[g], ids.data());
             enable_census(matchers[g], opt);
             enable_pairs(matchers[g], opt);
+            enable_indel(matchers[g], opt);
             if (g_timing) info("(timing) matcher on device %d created; anonymous resident memory %zu MB.", opt.devices[g], rss_anon_mb());
             fqtk_demux_config cfg;
             std::memset(&cfg, 0, sizeof cfg);
@@ -1667,6 +1723,7 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
     std::string err;
     write_top_unmatched(opt, matchers, L);
     write_index_pairs(opt, matchers, samples);
+    write_indel_rescue(opt, matchers, samples);
     if (opt.quality_metrics) {   // the devices' tables, summed (fqtk_demuxer_quality ADDS)
         QualityTable qt;
         qt.init(S, n_inputs);
@@ -1768,6 +1825,29 @@ int main(int argc, char **argv) {
             die("invalid use of '--index-pairs': the index-pair tally takes exactly two sample-barcode (B) segments of fixed length over all read "
                 "structures, these have " + std::to_string(lens.size()) + (lens.size() == 2 ? ", one of them of variable length" : ""));
         opt.pairs_len_a = (uint32_t)lens[0];
+    }
+    if (opt.indel_rescue) {   // what the rescue does not take: said here, before any input is opened (the host routers match through the same
+                              // entry points as the GPU record pipeline, so --host-output needs no word)
+        if (opt.weighted)
+            die("invalid use of '--indel-rescue' with '--quality-weighted': the rescue is a second look behind the mismatch-count rule; "
+                "quality-weighted assignment has its own notion of cost and is not rescued");
+        for (const ReadStructure &r : plan.rs)
+            for (const ReadSegment &seg : r.segments)
+                if (seg.kind == SegType::SampleBarcode && !seg.has_length())
+                    die("invalid use of '--indel-rescue': a sample-barcode segment of variable length ('+B') is not taken; "
+                        "the rescue examines templates whose sample barcode has the sample sheet's length");
+        if (opt.max_edits + opt.min_edit_delta == 0 || opt.max_edits + opt.min_edit_delta > 16)
+            die("invalid value for '--indel-rescue': MAXEDITS + DELTA must be from 1 to 16, got " + std::to_string(opt.max_edits) + " + " +
+                std::to_string(opt.min_edit_delta));
+        std::vector<Sample> sheet;
+        std::string err;
+        if (load_samples(opt.sample_metadata, &sheet, &err) && !sheet.empty()) {
+            if (sheet[0].barcode.size() > 32)
+                die("invalid value for '--indel-rescue': the indel rescue takes sample barcodes of at most 32 bases, those of \"" +
+                    opt.sample_metadata + "\" have " + std::to_string(sheet[0].barcode.size()));
+            if (opt.max_edits >= sheet[0].barcode.size())
+                die("invalid value for '--indel-rescue': MAXEDITS must be below the sample barcodes' length, " + std::to_string(sheet[0].barcode.size()));
+        }
     }
     if (opt.weighted) {   // what the weighted rule does not take: said here, before any input is opened
         if (opt.host_output || env_on("FQTK_HOST_OUTPUT"))
@@ -1885,6 +1965,7 @@ int main(int argc, char **argv) {
             fqtk_matcher_set_sample_ids(matchers[g], ids.data());
             enable_census(matchers[g], opt);
             enable_pairs(matchers[g], opt);
+            enable_indel(matchers[g], opt);
             info("GPU barcode matcher ready on device %d (%llu memo entries).", opt.devices[g],
                  (unsigned long long)fqtk_matcher_memo_entries(matchers[g]));
         }
@@ -2387,6 +2468,7 @@ int main(int argc, char **argv) {
     std::string err;
     write_top_unmatched(opt, matchers, L);
     write_index_pairs(opt, matchers, samples);
+    write_indel_rescue(opt, matchers, samples);
     if (opt.quality_metrics) {
         for (size_t s = 0; s <= S; ++s)
             if (quality_total.row(s)[0] != counts[s]) die("internal error: the quality metrics' template counts differ from the per-sample counts");

@@ -298,6 +298,38 @@ int fqtk_matcher_pairs_dims(fqtk_matcher *m, uint32_t *u_a, uint32_t *u_b);
 int fqtk_matcher_pairs_index(fqtk_matcher *m, int which, uint32_t i, char *out);
 int fqtk_matcher_pairs_read(fqtk_matcher *m, uint64_t *matrix, uint64_t *skipped);
 
+/* ---- indel rescue of the unmatched reads: one inserted or deleted base shifts every base behind it ------------------
+ * Every rule above counts substitutions only, so a read with an indel inside its index sits many mismatches from its own
+ * sample and comes out None.  No counterpart in the reference.  Opt-in, owned by the handle: one more kernel behind a batch's
+ * own, on the batch's stream and IN FRONT of the census and the pair tally, gives the None reads of exactly barcode_len bases
+ * (stride >= barcode_len, and no obs_len or obs_len[i] == barcode_len) a second look under an edit-distance rule; out[], the
+ * counts, the census, the pair tally and the record pipeline of fqtk_demux.h see the rescued result.  OFF (the default): no
+ * kernel is launched, no memory is taken, every result is what it is without these entry points.  The weighted calls below are
+ * never rescued.  The rule, all integer, L = barcode_len:
+ *   mis(r, s) = enc(r) & ~enc(s) != 0     (enc as everywhere else; a byte that encodes to 0 never mismatches)
+ *   D[0][j] = j, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + mis(read[i-1], sample[j-1]), D[i-1][j] + 1, D[i][j-1] + 1)
+ *   dist = min(min over j of D[L][j], min over i of D[i][L])      the sequence-Levenshtein distance: the last row takes an
+ *          inserted base (the barcode's tail is pushed out of the read), the last column a deleted one (adapter bases pulled in)
+ *   sat = max_edits + max(min_edit_delta, 1); every distance is taken as min(dist, sat), which changes no decision (with a
+ *          delta of 0 the cap sits one above max_edits, so that a capped distance is never accepted)
+ *   best = the lowest distance, idx = the LOWEST s that has it, next = the second smallest with multiplicity (sat for a table
+ *   of one sample); the read STAYS None iff best > max_edits or next - best < min_edit_delta, and is then not written at all.
+ * A rescued read: idx = s, best = 0x80 | best, next = next -- bit 7 of `best` says "an edit distance, not a mismatch count"
+ * (so the read is neither a perfect nor a one-mismatch match to whoever reads `best`).  With counts: +1 at s, -1 at S.
+ * The handle's own counters: rescued[s] = reads rescued into s, rescued[S] = reads examined and left None; skipped = None reads
+ * of another length.  Per batch with stride >= barcode_len:  sum(rescued) + skipped == None results of the matcher's kernels.
+ * Device memory: 64 bytes per sample and four bases, 8 bytes per sample.
+ *
+ * enable: FQTK_EINVAL when barcode_len > 32, when max_edits + min_edit_delta is 0 or above 16, or when max_edits >=
+ * barcode_len (the matcher stays as it was); FQTK_ENOMEM.  Again: the new parameters, counters cleared.  disable frees
+ * everything (fqtk_matcher_destroy does, too); reset clears the counters.  All three wait for the device to drain first.
+ * read: synchronises the device and copies rescued (S + 1) and skipped; either pointer may be NULL.  After disable it returns
+ * the counters as disable found them, until the next enable; FQTK_EINVAL ("the indel rescue is not enabled") before any enable. */
+int fqtk_matcher_indel_enable(fqtk_matcher *m, uint32_t max_edits, uint32_t min_edit_delta);
+int fqtk_matcher_indel_disable(fqtk_matcher *m);
+int fqtk_matcher_indel_reset(fqtk_matcher *m);
+int fqtk_matcher_indel_read(fqtk_matcher *m, uint64_t *rescued, uint64_t *skipped);
+
 /* ---- quality-weighted assignment: a mismatch costs what the sequencer said about that base ---------------------------
  * No counterpart in the reference, whose rule counts every mismatch as 1.  Here (all integer):
  *   w[i]    = clamp(qual[i] - 33, 0, 93)        every byte value is defined: below '!' is 0, above '~' is 93
