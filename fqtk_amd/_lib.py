@@ -151,6 +151,12 @@ SIGNATURES = [
                                                      C.c_void_p, C.c_void_p]),
     ("fqtk_matcher_assign_weighted_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fqtk_matcher_set_per_index", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("fqtk_matcher_per_index_kind", C.c_int, [C.c_void_p]),
+    ("fqtk_matcher_set_per_index_kind", C.c_int, [C.c_void_p, C.c_int]),
+    ("fqtk_matcher_assign_per_index_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("fqtk_matcher_assign_per_index_batch_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p]),
     ("fqtk_matchers_allreduce_counts", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
     # include/fqtk_bgzf.h
     ("fqtk_bgzf_last_error", C.c_char_p, []),
@@ -176,6 +182,7 @@ SIGNATURES = [
     ("fqtk_demuxer_flush", C.c_int, [C.c_void_p, C.POINTER(fqtk_demux_result)]),
     ("fqtk_demuxer_counts", C.c_int, [C.c_void_p, C.c_void_p]),
     ("fqtk_demuxer_weighted_enable", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("fqtk_demuxer_per_index_enable", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("fqtk_demuxer_quality_enable", C.c_int, [C.c_void_p]),
     ("fqtk_demuxer_quality_row_words", C.c_uint32, [C.c_void_p]),
     ("fqtk_demuxer_quality", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -244,6 +244,41 @@ class BarcodeMatcher:
         _check(self._lib.fqtk_matcher_assign_weighted_batch_device(self._h, d_obs or None, d_qual or None, stride, n, d_out or None,
                                                                    d_costs or None, d_counts or None, stream or None))
 
+    # ---- per-index mismatch budgets (fqtk_matcher_set_per_index / fqtk_matcher_assign_per_index_batch*) ----------------
+    PER_INDEX_OFF, PER_INDEX_SCAN, PER_INDEX_LDS = 0, 1, 2
+
+    def set_per_index(self, len_a: int, mm_a: int, delta_a: int, mm_b: int, delta_b: int) -> None:
+        """Turns the per-index calls on: index 1 = the first len_a bases, index 2 = the rest, each matched against the distinct
+        values of that index with its own (max_mismatches, min_mismatch_delta); the read goes to the sample whose pair it is.
+        ValueError for barcodes of more than 32 bases, len_a of 0 or barcode_len, an index of more than 16 bases."""
+        _check(self._lib.fqtk_matcher_set_per_index(self._h, int(len_a), int(mm_a), int(delta_a), int(mm_b), int(delta_b)))
+
+    @property
+    def per_index_kind(self) -> int:
+        """What the next per-index batch runs: PER_INDEX_OFF (before set_per_index), PER_INDEX_SCAN, PER_INDEX_LDS (two LDS memos)."""
+        return int(self._lib.fqtk_matcher_per_index_kind(self._h))
+
+    @per_index_kind.setter
+    def per_index_kind(self, kind: int) -> None:
+        _check(self._lib.fqtk_matcher_set_per_index_kind(self._h, int(kind)))
+
+    def assign_batch_per_index(self, obs: np.ndarray, counts: bool = True):
+        """obs: uint8 [n, stride >= barcode_len] (host), every read barcode_len bases (after set_per_index).
+        Returns (matches[MATCH_DTYPE n], counts u64[S+1] or None)."""
+        obs = np.ascontiguousarray(obs, dtype=np.uint8)
+        assert obs.ndim == 2
+        n, stride = obs.shape
+        out = np.empty(n, dtype=MATCH_DTYPE)
+        cnt = np.zeros(self.n_samples + 1, dtype=np.uint64) if counts else None
+        _check(self._lib.fqtk_matcher_assign_per_index_batch(self._h, obs.ctypes.data, stride, n, out.ctypes.data,
+                                                             cnt.ctypes.data if counts else None))
+        return out, cnt
+
+    def assign_batch_per_index_device(self, d_obs: int, stride: int, n: int, d_out: int, d_counts: int = 0, stream: int = 0) -> None:
+        """Zero-copy form of the per-index call (after set_per_index): raw device pointers and a hipStream_t handle.  Asynchronous."""
+        _check(self._lib.fqtk_matcher_assign_per_index_batch_device(self._h, d_obs or None, stride, n, d_out or None,
+                                                                    d_counts or None, stream or None))
+
     # ---- census of the unmatched barcodes (fqtk_matcher_census_*) -----------------------------------------------
     def enable_census(self, capacity: int = 0) -> None:
         """From here on every None read of every batch is tallied on the device by its barcode (0: 2^20 table slots)."""

@@ -201,6 +201,7 @@ struct fqtk_demuxer {
     unsigned long long *d_qual = nullptr;   // [n_samples + 1][Q.row_words]
     uint32_t qual_grid = 0;                 // FQTK_QUALITY_GRID=k (tests, A/B runs): at most k workgroups, so that a small chunk takes many rounds
     bool weighted = false;                  // quality-weighted assignment (fqtk_demuxer_weighted_enable)
+    bool per_index = false;                 // per-index mismatch budgets (fqtk_demuxer_per_index_enable)
     std::vector<fqtk_demux_segment> t_segs; // the T segments of all inputs as configured, in input order, wanted as files or not
     std::vector<uint32_t> t_seg_input;      // ... and whose each is
 };
@@ -594,6 +595,8 @@ static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, 
         hipLaunchKernelGGL(k_extract_qual, dim3(g256), dim3(256), 0, A, T, C, n, stride, s.skip.p, s.bq.p, s.d_status);
         DX_TRY(hipGetLastError());
         if ((rc = fqtk_matcher_assign_weighted_batch_device(d->m, s.obs.p, s.bq.p, stride, n, s.res.p, nullptr, nullptr, A)) != FQTK_OK) return rc;
+    } else if (d->per_index) {   // each index against its own list (every row holds barcode_len bytes: no lens)
+        if ((rc = fqtk_matcher_assign_per_index_batch_device(d->m, s.obs.p, stride, n, s.res.p, nullptr, A)) != FQTK_OK) return rc;
     } else if ((rc = fqtk_matcher_assign_batch_device(d->m, s.obs.p, stride, C.use_lens ? s.lens.p : nullptr, n, s.res.p, nullptr, A)) != FQTK_OK) return rc;
     if ((rc = fqtk::internal::take_device_error(d->m, A, &s.d_status->matcher_err)) != FQTK_OK) return rc;
     DX_TRY(hipEventRecord(s.ev[2], A));
@@ -1455,9 +1458,22 @@ int fqtk_demuxer_weighted_enable(fqtk_demuxer *d, uint32_t max_cost, uint32_t mi
     if (d->C.variable_bc || d->C.fixed_bc_len != d->C.barcode_len)
         return set_error(FQTK_EINVAL, "quality-weighted assignment takes sample-barcode (B) segments of fixed length that add up to the barcodes' length");
     if (d->quality) return set_error(FQTK_EINVAL, "quality-weighted assignment and the quality tally do not combine: its match columns read a saturated cost");
+    if (d->per_index) return set_error(FQTK_EINVAL, "per-index assignment and quality-weighted assignment do not combine: each is a rule of its own");
     const int rc = fqtk_matcher_set_weighted(d->m, max_cost, min_cost_delta);   // (its message stands)
     if (rc != FQTK_OK) return rc;
     d->weighted = true;
+    return FQTK_OK;
+}
+
+int fqtk_demuxer_per_index_enable(fqtk_demuxer *d, uint32_t mm_a, uint32_t delta_a, uint32_t mm_b, uint32_t delta_b) {
+    if (!d) return set_error(FQTK_EINVAL, "NULL argument");
+    if (d->chunk_no) return set_error(FQTK_EINVAL, "per-index assignment is enabled before the first chunk is submitted");
+    if (d->weighted) return set_error(FQTK_EINVAL, "per-index assignment and quality-weighted assignment do not combine: each is a rule of its own");
+    if (d->C.n_b != 2 || d->C.variable_bc || d->C.fixed_bc_len != d->C.barcode_len)
+        return set_error(FQTK_EINVAL, "per-index assignment takes exactly two sample-barcode (B) segments of fixed length that add up to the barcodes' length");
+    const int rc = fqtk_matcher_set_per_index(d->m, (uint32_t)d->C.bseg[0].length, mm_a, delta_a, mm_b, delta_b);   // (its message stands)
+    if (rc != FQTK_OK) return rc;
+    d->per_index = true;
     return FQTK_OK;
 }
 

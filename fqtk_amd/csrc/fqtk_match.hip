@@ -41,6 +41,7 @@ extern "C" int fqtk_dev_phase_cycles(unsigned long long *out16) {
 #include "census_kernels.hip.h"
 #include "pair_kernels.hip.h"
 #include "indel_kernels.hip.h"
+#include "per_index_kernels.hip.h"
 
 namespace {
 
@@ -203,6 +204,7 @@ struct fqtk_matcher {
     fqtk::Census census;                       // opt-in table of the unmatched barcodes (census_kernels.hip.h); off: nothing allocated
     fqtk::Pairs pairs;                         // opt-in index-pair tally of the unmatched reads (pair_kernels.hip.h); off: nothing allocated
     fqtk::Indel indel;                         // opt-in indel rescue of the unmatched reads (indel_kernels.hip.h); off: nothing allocated
+    fqtk::PerIndex per_index;                  // per-index budgets as an assignment mode (per_index_kernels.hip.h): its own entry points; off until set_per_index
     Slot slots[kNumSlots];
 };
 
@@ -399,6 +401,17 @@ int launch_weighted(const fqtk_matcher *m, const fqtk::MatchParams &P, const voi
     W.max_cost = m->max_cost;
     W.min_cost_delta = m->min_cost_delta;
     const int rc = pl.kb == 3 ? launch_weighted_vec<3>(m, W, stream) : launch_weighted_vec<6>(m, W, stream);
+    if (rc != FQTK_OK || !(m->census.on() || m->pairs.on())) return rc;
+    if (m->census.on()) {
+        const int rc_census = fqtk::census_launch(m->census, P, m->num_cus, stream);
+        if (rc_census != FQTK_OK) return rc_census;
+    }
+    return m->pairs.on() ? fqtk::pairs_launch(m->pairs, P, m->num_cus, stream) : FQTK_OK;
+}
+
+// A per-index batch: per_index_kernel or the per-index scan and, when they are on, the census and the pair tally behind it.
+int launch_per_index(const fqtk_matcher *m, const fqtk::MatchParams &P, hipStream_t stream) {
+    const int rc = fqtk::per_index_launch(m->per_index, P, m->num_cus, stream, m->ldsm_big_lds_ok);
     if (rc != FQTK_OK || !(m->census.on() || m->pairs.on())) return rc;
     if (m->census.on()) {
         const int rc_census = fqtk::census_launch(m->census, P, m->num_cus, stream);
@@ -1646,6 +1659,7 @@ void fqtk_matcher_destroy(fqtk_matcher *m) {
     (void)fqtk::census_disable(m->census);
     (void)fqtk::pairs_disable(m->pairs);
     (void)fqtk::indel_disable(m->indel);
+    (void)fqtk::per_index_off(m->per_index);
     if (m->d_table) (void)hipFree(m->d_table);
     if (m->d_lut) (void)hipFree(m->d_lut);
     if (m->d_err) (void)hipFree(m->d_err);
@@ -1878,6 +1892,76 @@ int fqtk_matcher_assign_weighted_batch(fqtk_matcher *m, const uint8_t *obs, cons
         if ((rc = launch_weighted(m, P, s.d_qual, costs ? s.d_costs : nullptr, s.stream)) != FQTK_OK) return rc;
         HIP_TRY(hipMemcpyAsync(out + done, s.d_out, (size_t)cur * sizeof(fqtk_match_t), hipMemcpyDeviceToHost, s.stream));
         if (costs) HIP_TRY(hipMemcpyAsync(costs + done, s.d_costs, (size_t)cur * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipStreamSynchronize(s.stream));
+    }
+    if (counts) {
+        std::vector<unsigned long long> tmp(bins);
+        HIP_TRY(hipMemcpy(tmp.data(), m->d_counts_sync, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < bins; ++b) counts[b] += (uint64_t)tmp[b];
+    }
+    return FQTK_OK;
+}
+
+// ---- per-index mismatch budgets (per_index_kernels.hip.h) ----------------------------------------------------------------
+int fqtk_matcher_set_per_index(fqtk_matcher *m, uint32_t len_a, uint32_t mm_a, uint32_t delta_a, uint32_t mm_b, uint32_t delta_b) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    HIP_TRY(hipSetDevice(m->device));
+    const uint32_t mm[2] = {mm_a, mm_b}, delta[2] = {delta_a, delta_b};
+    return fqtk::per_index_set(m->per_index, m->barcodes_upper, m->L, len_a, mm, delta, enc_byte, fqtk::kLdsMemoMaxBytes);
+}
+
+int fqtk_matcher_per_index_kind(const fqtk_matcher *m) {
+    if (!m || !m->per_index.on) return FQTK_PER_INDEX_OFF;
+    return m->per_index.lds_form() ? FQTK_PER_INDEX_LDS : FQTK_PER_INDEX_SCAN;
+}
+
+int fqtk_matcher_set_per_index_kind(fqtk_matcher *m, int kind) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    if (kind != FQTK_PER_INDEX_SCAN && kind != FQTK_PER_INDEX_LDS) return fail(FQTK_EINVAL, "per-index kind must be FQTK_PER_INDEX_SCAN or FQTK_PER_INDEX_LDS");
+    m->per_index.pin_scan = kind == FQTK_PER_INDEX_SCAN;
+    return FQTK_OK;
+}
+
+static int check_per_index_args(const fqtk_matcher *m, const void *obs, uint32_t stride, uint64_t n, const void *out) {
+    if (!m) return fail(FQTK_EINVAL, "matcher is NULL");
+    if (!m->per_index.on) return fail(FQTK_EINVAL, "per-index assignment is not set up: call fqtk_matcher_set_per_index() first");
+    if (n == 0) return FQTK_OK;
+    if (!obs || !out) return fail(FQTK_EINVAL, "obs/out is NULL");
+    if (stride < m->L) return fail(FQTK_EINVAL, "stride < barcode_len: per-index assignment has no obs_len form");
+    return FQTK_OK;
+}
+
+int fqtk_matcher_assign_per_index_batch_device(fqtk_matcher *m, const void *d_obs, uint32_t stride, uint64_t n, void *d_out, void *d_counts,
+                                               void *hip_stream) {
+    const int rc = check_per_index_args(m, d_obs, stride, n, d_out);
+    if (rc != FQTK_OK || n == 0) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    const fqtk::MatchParams P = make_params(m, d_obs, stride, nullptr, n, d_out, d_counts, kDeviceErrWord);
+    return launch_per_index(m, P, static_cast<hipStream_t>(hip_stream));
+}
+
+int fqtk_matcher_assign_per_index_batch(fqtk_matcher *m, const uint8_t *obs, uint32_t stride, uint64_t n, fqtk_match_t *out, uint64_t *counts) {
+    int rc = check_per_index_args(m, obs, stride, n, out);
+    if (rc != FQTK_OK || n == 0) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    if ((rc = ensure_slot(m, kSyncSlot0)) != FQTK_OK) return rc;
+    Slot &s = m->slots[kSyncSlot0];   // private to the synchronous calls; one chunk at a time
+    if (s.busy) return fail(FQTK_EINVAL, "slot is busy");
+    const size_t bins = (size_t)m->S + 1;
+    if (counts) {
+        HIP_TRY(hipMemset(m->d_counts_sync, 0, bins * sizeof(unsigned long long)));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // must land before the kernels on the non-blocking slot stream
+    }
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, (256ull << 20) / stride));
+    for (uint64_t done = 0; done < n; done += chunk) {
+        const uint64_t cur = std::min(chunk, n - done);
+        const size_t bytes = (size_t)cur * stride;
+        if ((rc = ensure_cap(s.d_obs, s.obs_cap, bytes + 16)) != FQTK_OK) return rc;
+        if ((rc = ensure_cap(s.d_out, s.out_cap, (size_t)cur)) != FQTK_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(s.d_obs, obs + done * stride, bytes, hipMemcpyHostToDevice, s.stream));
+        const fqtk::MatchParams P = make_params(m, s.d_obs, stride, nullptr, cur, s.d_out, counts ? m->d_counts_sync : nullptr, kSyncSlot0);
+        if ((rc = launch_per_index(m, P, s.stream)) != FQTK_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(out + done, s.d_out, (size_t)cur * sizeof(fqtk_match_t), hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipStreamSynchronize(s.stream));
     }
     if (counts) {

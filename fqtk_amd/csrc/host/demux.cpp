@@ -205,6 +205,8 @@ struct Options {
     bool weighted = false;           // --quality-weighted MAXCOST,DELTA: a mismatch costs the base's quality (fqtk_demuxer_weighted_enable)
     unsigned long max_cost = 0, min_cost_delta = 0;
     bool mismatch_flags_given = false;   //   --max-mismatches / --min-mismatch-delta were given: ignored with --quality-weighted, and said so
+    bool per_index = false;          // --per-index-mismatches M1,M2: each of the two sample-barcode segments has a budget of its own (fqtk_demuxer_per_index_enable)
+    unsigned long per_index_mm[2] = {0, 0};
     bool indel_rescue = false;       // --indel-rescue MAXEDITS,DELTA: unmatched templates get a second look under an edit-distance rule on the device
     unsigned long max_edits = 0, min_edit_delta = 0;
 };
@@ -254,6 +256,13 @@ const char *kUsage =
     "                                              or the next best is less than DELTA away; --max-mismatches and --min-mismatch-delta are ignored;\n"
     "                                              B segments of fixed length, at most 32 bases and 16384 samples; not with --host-output or\n"
     "                                              --quality-metrics (additive flag)\n"
+    "      --per-index-mismatches <M1,M2>          match each of the two sample-barcode segments on its own, as bcl2fastq's --barcode-mismatches\n"
+    "                                              does: index 1 against the sample sheet's distinct first indexes with at most M1 mismatches,\n"
+    "                                              index 2 against the distinct second indexes with at most M2, each with --min-mismatch-delta as\n"
+    "                                              its delta; the template goes to the sample whose pair of indexes it is; --max-mismatches is\n"
+    "                                              ignored; exactly two B segments of fixed length, at most 16 bases each; works with --index-pairs,\n"
+    "                                              --top-unmatched and --quality-metrics; not with --quality-weighted, --indel-rescue or\n"
+    "                                              --host-output (additive flag)\n"
     "      --indel-rescue <MAXEDITS,DELTA>         give the unmatched templates a second look on the device under the edit distance to every\n"
     "                                              sample barcode (substitutions, one inserted or deleted base and what it shifts in or out):\n"
     "                                              a template whose best distance is at most MAXEDITS and whose next best is at least DELTA\n"
@@ -334,6 +343,14 @@ Options parse_args(int argc, char **argv) {
                 o.max_cost > 0xFFFFFFFFul || o.min_cost_delta > 0xFFFFFFFFul)
                 die("invalid value '" + v + "' for '--quality-weighted': expected MAXCOST,DELTA (two non-negative integers)");
             o.weighted = true;
+        }
+        else if (a == "--per-index-mismatches") {
+            const std::string v = single();
+            const size_t q = v.find(',');
+            if (q == std::string::npos || !parse_ulong(v.substr(0, q), &o.per_index_mm[0]) || !parse_ulong(v.substr(q + 1), &o.per_index_mm[1]) ||
+                o.per_index_mm[0] > 255 || o.per_index_mm[1] > 255)
+                die("invalid value '" + v + "' for '--per-index-mismatches': expected M1,M2 (two non-negative integers)");
+            o.per_index = true;
         }
         else if (a == "--indel-rescue") {
             const std::string v = single();
@@ -884,6 +901,9 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
             if (opt.quality_metrics && fqtk_demuxer_quality_enable(demuxers[g]) != FQTK_OK) die(std::string("cannot set up the quality metrics: ") + fqtk_last_error());
             if (opt.weighted && fqtk_demuxer_weighted_enable(demuxers[g], (uint32_t)opt.max_cost, (uint32_t)opt.min_cost_delta) != FQTK_OK)
                 die(std::string("cannot set up quality-weighted assignment: ") + fqtk_last_error());
+            if (opt.per_index && fqtk_demuxer_per_index_enable(demuxers[g], (uint32_t)opt.per_index_mm[0], (uint32_t)opt.min_mismatch_delta,
+                                                               (uint32_t)opt.per_index_mm[1], (uint32_t)opt.min_mismatch_delta) != FQTK_OK)
+                die(std::string("cannot set up per-index assignment: ") + fqtk_last_error());
             info("GPU barcode matcher and record pipeline ready on device %d (%llu memo entries).", opt.devices[g],
                  (unsigned long long)fqtk_matcher_memo_entries(matchers[g]));
             if (g_timing) info("(timing) anonymous resident memory: %zu MB.", rss_anon_mb());
@@ -1849,6 +1869,30 @@ int main(int argc, char **argv) {
                 die("invalid value for '--indel-rescue': MAXEDITS must be below the sample barcodes' length, " + std::to_string(sheet[0].barcode.size()));
         }
     }
+    if (opt.per_index) {   // what the per-index rule does not take: said here, before any input is opened
+        if (opt.weighted)
+            die("invalid use of '--per-index-mismatches' with '--quality-weighted': each is an assignment rule of its own, "
+                "and a template is assigned by one of them");
+        if (opt.indel_rescue)
+            die("invalid use of '--per-index-mismatches' with '--indel-rescue': the rescue is a second look behind the whole-barcode "
+                "mismatch-count rule; per-index assignment is not rescued");
+        if (opt.host_output || env_on("FQTK_HOST_OUTPUT"))
+            die("invalid use of '--per-index-mismatches' with '--host-output': the host routers match whole barcodes; "
+                "per-index assignment runs in the GPU record pipeline only");
+        std::vector<int> lens;
+        for (const ReadStructure &r : plan.rs)
+            for (const ReadSegment &seg : r.segments)
+                if (seg.kind == SegType::SampleBarcode) lens.push_back(seg.has_length() ? (int)seg.length : -1);
+        if (lens.size() != 2 || lens[0] < 0 || lens[1] < 0)
+            die("invalid use of '--per-index-mismatches': per-index assignment takes exactly two sample-barcode (B) segments of fixed length over all "
+                "read structures, these have " + std::to_string(lens.size()) + (lens.size() == 2 ? ", one of them of variable length" : ""));
+        if (lens[0] > 16 || lens[1] > 16)
+            die("invalid use of '--per-index-mismatches': per-index assignment takes indexes of at most 16 bases, these have " +
+                std::to_string(lens[0]) + " + " + std::to_string(lens[1]));
+        if (opt.mismatch_flags_given)
+            std::fprintf(stderr, "Note: --max-mismatches is ignored with --per-index-mismatches (%lu,%lu decide; --min-mismatch-delta %lu is each index's delta).\n",
+                         opt.per_index_mm[0], opt.per_index_mm[1], opt.min_mismatch_delta);
+    }
     if (opt.weighted) {   // what the weighted rule does not take: said here, before any input is opened
         if (opt.host_output || env_on("FQTK_HOST_OUTPUT"))
             die("invalid use of '--quality-weighted' with '--host-output': the host routers carry no quality rows of the sample barcodes; "
@@ -1950,6 +1994,8 @@ int main(int argc, char **argv) {
         if (gpu_output_supported(plan, &why)) run_gpu_output(opt, plan, samples, sources, skip_few);   // does not return
         if (opt.weighted)
             die("invalid use of '--quality-weighted': the GPU record pipeline does not take this configuration (" + why + "), and the host routers carry no quality rows");
+        if (opt.per_index)
+            die("invalid use of '--per-index-mismatches': the GPU record pipeline does not take this configuration (" + why + "), and the host routers match whole barcodes");
         info("The GPU record pipeline does not take this configuration (%s): records are formatted and compressed on the host.", why.c_str());
     }
     const size_t G = opt.devices.size();

@@ -51,9 +51,10 @@ struct PairsParams {
     uint32_t mm_i, delta_i;      // the per-index max_mismatches / min_mismatch_delta
 };
 
-// One list (n entries from `tab` on) over one read: the assigned entry, or n = unassigned (barcode_matching.rs:119-159 on one index).
-__device__ __forceinline__ uint32_t pairs_assign(const_u32x4_ptr tab, uint32_t n, const Planes<1> &o, uint32_t mm_i, uint32_t delta_i) {
-    uint32_t best = kKeyInit, second = kKeyInit;
+// One list (n entries from `tab` on) over one read: the packed keys (mismatches << 16 | entry) of the best and the second best
+// entry, kKeyInit where there is none (per_index_kernels.hip.h turns them into a result; pairs_assign below into a cell).
+__device__ __forceinline__ void pairs_scan(const_u32x4_ptr tab, uint32_t n, const Planes<1> &o, uint32_t &best, uint32_t &second) {
+    best = second = kKeyInit;
     constexpr int G = 4;   // 16 dwords = one s_load_dwordx16, the next group asked for before this one's VALU work
     const uint32_t ngroups = n / G;
     SampleGroup<1, G> cur, nxt;
@@ -69,6 +70,12 @@ __device__ __forceinline__ uint32_t pairs_assign(const_u32x4_ptr tab, uint32_t n
         one.load(tab, s);
         update<1>(o, one.e[0], s, best, second);
     }
+}
+
+// The assigned entry of one list, or n = unassigned (barcode_matching.rs:119-159 on one index).
+__device__ __forceinline__ uint32_t pairs_assign(const_u32x4_ptr tab, uint32_t n, const Planes<1> &o, uint32_t mm_i, uint32_t delta_i) {
+    uint32_t best, second;
+    pairs_scan(tab, n, o, best, second);
     const uint32_t bm = best >> 16, nm = second >> 16;   // one entry: second stays at its initial 255
     return (bm > mm_i || (nm - bm) < delta_i) ? n : (best & 0xFFFFu);
 }
@@ -218,25 +225,17 @@ inline int pairs_reset(Pairs &p) {
     return FQTK_OK;
 }
 
-// barcodes = the table as the matcher keeps it (upper case), enc = the reference's encode() of one byte.
-inline int pairs_enable(Pairs &p, const std::vector<std::string> &barcodes, uint32_t L, uint32_t len_a, uint32_t mm_i, uint32_t delta_i,
-                        uint8_t (*enc)(uint8_t)) {
-    if (L > kPairsMaxLen)
-        return internal::set_error(FQTK_EINVAL, "the index-pair tally takes barcodes of at most 32 bases; this table's have " + std::to_string(L));
-    if (len_a == 0 || len_a >= L)
-        return internal::set_error(FQTK_EINVAL, "the split point len_a must leave both indexes a base: 1 <= len_a < " + std::to_string(L) +
-                                                    ", got " + std::to_string(len_a));
-    std::vector<std::string> index[2];
+// A and B of include/fqtk_match.h: the distinct strings barcode_s[0 : len_a] and barcode_s[len_a :], each in order of first appearance.
+inline void pairs_split_indexes(const std::vector<std::string> &barcodes, uint32_t len_a, std::vector<std::string> (&index)[2]) {
     for (const std::string &b : barcodes) {
         const std::string part[2] = {b.substr(0, len_a), b.substr(len_a)};
         for (int w = 0; w < 2; ++w)
             if (std::find(index[w].begin(), index[w].end(), part[w]) == index[w].end()) index[w].push_back(part[w]);
     }
-    const uint64_t cells = (uint64_t)(index[0].size() + 1) * (index[1].size() + 1);
-    if (cells > kPairsMaxCells)
-        return internal::set_error(FQTK_EINVAL, "the index-pair matrix would have " + std::to_string(cells) + " cells; at most 2^24 (128 MiB) are tallied");
-    const int rc = pairs_disable(p);
-    if (rc != FQTK_OK) return rc;
+}
+
+// [u_a + u_b][4] pre-inverted planes over the whole barcode's word: A's entries, then B's, the positions outside an index left 0.
+inline std::vector<uint32_t> pairs_plane_table(const std::vector<std::string> (&index)[2], uint32_t len_a, uint8_t (*enc)(uint8_t)) {
     std::vector<uint32_t> tab((index[0].size() + index[1].size()) * 4, 0u);
     size_t e = 0;
     for (int w = 0; w < 2; ++w)
@@ -248,6 +247,25 @@ inline int pairs_enable(Pairs &p, const std::vector<std::string> &barcodes, uint
             }
             ++e;
         }
+    return tab;
+}
+
+// barcodes = the table as the matcher keeps it (upper case), enc = the reference's encode() of one byte.
+inline int pairs_enable(Pairs &p, const std::vector<std::string> &barcodes, uint32_t L, uint32_t len_a, uint32_t mm_i, uint32_t delta_i,
+                        uint8_t (*enc)(uint8_t)) {
+    if (L > kPairsMaxLen)
+        return internal::set_error(FQTK_EINVAL, "the index-pair tally takes barcodes of at most 32 bases; this table's have " + std::to_string(L));
+    if (len_a == 0 || len_a >= L)
+        return internal::set_error(FQTK_EINVAL, "the split point len_a must leave both indexes a base: 1 <= len_a < " + std::to_string(L) +
+                                                    ", got " + std::to_string(len_a));
+    std::vector<std::string> index[2];
+    pairs_split_indexes(barcodes, len_a, index);
+    const uint64_t cells = (uint64_t)(index[0].size() + 1) * (index[1].size() + 1);
+    if (cells > kPairsMaxCells)
+        return internal::set_error(FQTK_EINVAL, "the index-pair matrix would have " + std::to_string(cells) + " cells; at most 2^24 (128 MiB) are tallied");
+    const int rc = pairs_disable(p);
+    if (rc != FQTK_OK) return rc;
+    const std::vector<uint32_t> tab = pairs_plane_table(index, len_a, enc);
     FQTK_PAIRS_TRY(hipMalloc(reinterpret_cast<void **>(&p.d_tab), tab.size() * sizeof(uint32_t)));
     FQTK_PAIRS_TRY(hipMemcpy(p.d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (hipMalloc(reinterpret_cast<void **>(&p.d_mat), (cells + 1) * sizeof(unsigned long long)) != hipSuccess) {   // on() only from here

@@ -211,6 +211,10 @@ class Demuxer:
         _check(self._lib.fqtk_demuxer_counts(self._h, c.ctypes.data))
         return c
 
+    def enable_per_index(self, mm_a: int, delta_a: int, mm_b: int, delta_b: int) -> None:
+        """Per-index mismatch budgets for every chunk's templates (before the first submit; exactly two fixed-length B segments)."""
+        _check(self._lib.fqtk_demuxer_per_index_enable(self._h, int(mm_a), int(delta_a), int(mm_b), int(delta_b)))
+
     def enable_weighted(self, max_cost: int, min_cost_delta: int) -> None:
         """Quality-weighted assignment of every chunk's templates from the next chunk on (before the first submit; fixed-length B segments)."""
         _check(self._lib.fqtk_demuxer_weighted_enable(self._h, int(max_cost), int(min_cost_delta)))

@@ -243,6 +243,16 @@ int fqtk_demuxer_counts(fqtk_demuxer *d, uint64_t *counts);
  * Not enabled: no kernel runs, nothing is allocated. */
 int fqtk_demuxer_weighted_enable(fqtk_demuxer *d, uint32_t max_cost, uint32_t min_cost_delta);
 
+/* ---- per-index mismatch budgets for the chunks' templates (opt-in; the rule: fqtk_match.h, fqtk_matcher_set_per_index) ---------
+ * Once enabled, the match step of every chunk is fqtk_matcher_assign_per_index_batch_device: index 1 is the first sample-barcode
+ * (B) segment and takes (mm_a, delta_a), index 2 the second and takes (mm_b, delta_b); len_a is the first segment's length.  The
+ * matcher's max_mismatches / min_mismatch_delta play no part.  Everything behind the match step is unchanged; `best` is a true
+ * mismatch total, so the quality tally's perfect / one-mismatch columns keep their meaning and the two combine.
+ * Before the first submit.  FQTK_EINVAL: after a submit; anything but exactly two B segments of fixed length that add up to the
+ * barcodes' length; together with fqtk_demuxer_weighted_enable, in either order; what fqtk_matcher_set_per_index refuses
+ * (barcodes over 32 bases, an index over 16).  Not enabled: no kernel runs, nothing is allocated. */
+int fqtk_demuxer_per_index_enable(fqtk_demuxer *d, uint32_t mm_a, uint32_t delta_a, uint32_t mm_b, uint32_t delta_b);
+
 /* ---- per-sample yield and quality metrics, tallied on the device (opt-in) ---------------------------------------------------
  * Once enabled, every chunk adds one row of counters per sample (n_samples + 1 rows, unmatched last) for the templates it
  * does not drop:

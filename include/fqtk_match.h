@@ -362,6 +362,46 @@ int fqtk_matcher_assign_weighted_batch(fqtk_matcher *m, const uint8_t *obs, cons
 int fqtk_matcher_assign_weighted_batch_device(fqtk_matcher *m, const void *d_obs, const void *d_qual, uint32_t stride, uint64_t n,
                                               void *d_out, void *d_costs, void *d_counts, void *hip_stream);
 
+/* ---- per-index mismatch budgets: each index of a dual-index read is matched on its own -----------------------------------
+ * Every rule above counts mismatches over the whole concatenated barcode.  This is the other rule, the one bcl2fastq and BCL
+ * Convert apply (--barcode-mismatches 1,1): no counterpart in the reference.  All integer; L = barcode_len.
+ *   parameters  len_a with 0 < len_a < L; (mm_a, delta_a) for index 1 = positions [0, len_a); (mm_b, delta_b) for index 2 = [len_a, L)
+ *   A, B        the distinct strings barcode_s[0 : len_a] and barcode_s[len_a : L], each in order of first appearance: exactly
+ *               the lists of fqtk_matcher_pairs_enable above
+ *   per index   assigned against its list by the text under "assign" in the pairs section: a mismatch is
+ *               enc(read) & ~enc(index) != 0, best = the lowest count, the entry = the lowest one that has it, next = the second
+ *               smallest with multiplicity (255 for a list of one); the index is unassigned when best > mm_i or
+ *               next - best < delta_i.  No special cases for any byte value.
+ *   the read    None when either index is unassigned or when no sample has the pair (a, b); else idx = the LOWEST s with that
+ *               pair, best = best_a + best_b, next = min(255, min(next_a + best_b, best_a + next_b)).
+ * Scope: every row holds exactly L bases (stride >= L, no obs_len form), L <= 32, len_a <= 16 and L - len_a <= 16.  The matcher's
+ * max_mismatches / min_mismatch_delta play no part in these calls, and these calls none in the others.
+ * How it runs (results never depend on it): for plain A/C/G/T tables with mm_a, mm_b <= 1 whose image fits, two per-index memos,
+ * the index keys and a pair -> sample directory are resident in every CU's LDS and a read is two LDS look-ups
+ * (FQTK_PER_INDEX_LDS); every other table takes a per-index scan of each read (FQTK_PER_INDEX_SCAN).
+ * fqtk_matcher_per_index_kind() reports what the next batch runs (FQTK_PER_INDEX_OFF before set_per_index);
+ * fqtk_matcher_set_per_index_kind(m, FQTK_PER_INDEX_SCAN) pins the scan, FQTK_PER_INDEX_LDS means "best available": a tuning / test
+ * knob like fqtk_matcher_set_memo_kind, of no use to a caller who only wants results.
+ *
+ * set_per_index: builds A, B, the scan tables and the LDS image (again: with the new parameters).  FQTK_EINVAL for L > 32,
+ * len_a == 0 or >= L, an index longer than 16 bases (the matcher stays as it was); FQTK_ENOMEM.  Before it nothing is allocated
+ * and nothing is launched.  Device memory: 16 bytes per distinct index, 4 per distinct pair, at most 160 KiB of image.
+ * assign_per_index_batch: host pointers, synchronous, on a pipeline slot of its own like fqtk_matcher_assign_batch; counts NULL
+ * or S+1 counters that are ADDED to.  assign_per_index_batch_device: DEVICE pointers, enqueued on `hip_stream` without
+ * synchronising; d_counts NULL or S+1 uint64 accumulated with atomics.  Nothing is latched: there is no length error to raise.
+ * FQTK_EINVAL: before set_per_index, obs / out NULL, stride < barcode_len.
+ * With the census or the index-pair tally enabled they run behind such a batch as behind any other and see its None results
+ * (the pair tally keeps the two parameters of fqtk_matcher_pairs_enable).  The indel rescue never touches these calls. */
+#define FQTK_PER_INDEX_OFF 0
+#define FQTK_PER_INDEX_SCAN 1
+#define FQTK_PER_INDEX_LDS 2
+int fqtk_matcher_set_per_index(fqtk_matcher *m, uint32_t len_a, uint32_t mm_a, uint32_t delta_a, uint32_t mm_b, uint32_t delta_b);
+int fqtk_matcher_per_index_kind(const fqtk_matcher *m);
+int fqtk_matcher_set_per_index_kind(fqtk_matcher *m, int kind);
+int fqtk_matcher_assign_per_index_batch(fqtk_matcher *m, const uint8_t *obs, uint32_t stride, uint64_t n, fqtk_match_t *out, uint64_t *counts);
+int fqtk_matcher_assign_per_index_batch_device(fqtk_matcher *m, const void *d_obs, uint32_t stride, uint64_t n, void *d_out, void *d_counts,
+                                               void *hip_stream);
+
 /* ---- several GPUs in one process------------------------------------------------ */
 /* Templates are independent, so chunks shard over devices with no data-path exchange: one matcher per
  * device (the table is replicated by fqtk_matcher_create), chunk k goes to matcher k mod n.  The ONE
