@@ -30,6 +30,7 @@
 #include "inflate_internal.hpp"
 #include "matcher_internal.hpp"
 #include "quality_kernels.hip.h"
+#include "adapter_kernels.hip.h"
 
 namespace {
 using namespace fqtk::demux;
@@ -200,6 +201,11 @@ struct fqtk_demuxer {
     QualConfig Q{};
     unsigned long long *d_qual = nullptr;   // [n_samples + 1][Q.row_words]
     uint32_t qual_grid = 0;                 // FQTK_QUALITY_GRID=k (tests, A/B runs): at most k workgroups, so that a small chunk takes many rounds
+    // 3' adapter scan of the template reads (fqtk_demuxer_adapter_enable): level 2 of adapter_kernels.hip.h
+    bool adapters = false;
+    AdapterConfig A{};
+    unsigned long long *d_adapt = nullptr;  // [n_samples + 1][A.row_words]
+    uint32_t adapt_grid = 0;                // FQTK_ADAPTER_GRID=k, as qual_grid
     bool weighted = false;                  // quality-weighted assignment (fqtk_demuxer_weighted_enable)
     bool per_index = false;                 // per-index mismatch budgets (fqtk_demuxer_per_index_enable)
     std::vector<fqtk_demux_segment> t_segs; // the T segments of all inputs as configured, in input order, wanted as files or not
@@ -472,6 +478,7 @@ void fqtk_demuxer_destroy(fqtk_demuxer *d) {
     if (d->d_fs) (void)hipFree(d->d_fs);
     if (d->d_counts) (void)hipFree(d->d_counts);
     if (d->d_qual) (void)hipFree(d->d_qual);
+    if (d->d_adapt) (void)hipFree(d->d_adapt);
     if (d->d_tok) (void)hipFree(d->d_tok);
     for (hipStream_t st : {d->s_in, d->s_a, d->s_b, d->s_out}) if (st) (void)hipStreamDestroy(st);
     delete d;
@@ -621,6 +628,15 @@ static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, 
         const uint32_t grid = (uint32_t)std::min<uint64_t>((items + kQualGroups - 1) / kQualGroups, d->qual_grid ? d->qual_grid : (uint64_t)d->num_cus * 8u);
         hipLaunchKernelGGL(k_quality, dim3(grid), dim3(kQualBlock), use_lds ? n_counters * sizeof(uint32_t) : 0, A, T, d->Q, n, (const uint32_t *)s.res.p,
                            (const uint8_t *)s.skip.p, d->d_qual, n_counters, use_lds, (const ChunkStatus *)s.d_status);
+        DX_TRY(hipGetLastError());
+    }
+    if (d->adapters && d->A.n_ain) {   // (before ev_fmt as well: it reads the window's text; the matcher's results are behind it on this stream)
+        const uint32_t items = ((n + 3u) & ~3u) * d->A.n_ain;
+        const uint32_t n_counters = (C.n_samples + 1u) * d->A.row_words;
+        const uint32_t use_lds = n_counters <= kQualLdsCounters ? 1u : 0u;
+        const uint32_t grid = std::min<uint32_t>((items + kAdapterGroups - 1u) / kAdapterGroups, d->adapt_grid ? d->adapt_grid : (uint32_t)d->num_cus * 8u);
+        hipLaunchKernelGGL(k_adapter, dim3(grid), dim3(kAdapterBlock), (kAdapterGroups * kAdapterGroupWords + (use_lds ? n_counters : 0u)) * sizeof(uint32_t), A, T, d->A, n,
+                           (const uint32_t *)s.res.p, (const uint8_t *)s.skip.p, d->d_adapt, n_counters, use_lds, (const ChunkStatus *)s.d_status);
         DX_TRY(hipGetLastError());
     }
     if (T.window) {   // (before ev_fmt: the arena the window lies in may be reused once that event is reached)
@@ -1520,6 +1536,90 @@ int fqtk_demuxer_quality(fqtk_demuxer *d, uint64_t *out) {
     DX_TRY(hipStreamSynchronize(d->s_a));
     std::vector<unsigned long long> h(((size_t)d->C.n_samples + 1) * d->Q.row_words);
     DX_TRY(hipMemcpy(h.data(), d->d_qual, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) out[i] += (uint64_t)h[i];
+    return FQTK_OK;
+}
+
+int fqtk_demuxer_adapter_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap, uint32_t max_error_pct, uint32_t short_insert) {
+    if (!d || !adapters) return set_error(FQTK_EINVAL, "NULL argument");
+    if (d->chunk_no) return set_error(FQTK_EINVAL, "the adapter scan is enabled before the first chunk is submitted");
+    if (d->adapters) return set_error(FQTK_EINVAL, "the adapter scan is enabled once");
+    AdapterConfig A;
+    std::memset(&A, 0, sizeof A);
+    A.n_samples = d->C.n_samples;
+    A.short_insert = short_insert;
+    for (size_t q = 0; q < d->t_segs.size(); ++q) {   // (t_segs is in input order: an input's last T segment overwrites its earlier ones)
+        const uint32_t i = d->t_seg_input[q];
+        if (A.n_ain == 0 || A.ain[A.n_ain - 1u] != i) A.ain[A.n_ain++] = (uint8_t)i;
+        A.t_off[A.n_ain - 1u] = d->t_segs[q].offset;
+        A.t_len[A.n_ain - 1u] = d->t_segs[q].length;
+    }
+    A.row_words = kAdapterRowWords * A.n_ain;
+    if (min_overlap == 0) return set_error(FQTK_EINVAL, "the adapter scan takes a min_overlap of 1 or more");
+    if (max_error_pct > 30) return set_error(FQTK_EINVAL, "the adapter scan takes a max_error_pct of 0 to 30");
+    if (n_adapters == 0 || n_adapters > std::max<uint32_t>(A.n_ain, 1u))
+        return set_error(FQTK_EINVAL, "the adapter scan takes between 1 adapter and one per scanned input (an input with a template segment): n_adapters is " +
+                                          std::to_string(n_adapters) + ", scanned inputs " + std::to_string(A.n_ain));
+    std::vector<std::string> seqs;
+    for (uint32_t k = 0; k < n_adapters; ++k) {
+        if (!adapters[k]) return set_error(FQTK_EINVAL, "NULL argument");
+        std::string a(adapters[k]);
+        for (char &c : a) {
+            c = (char)((unsigned char)c & 0xDFu);
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return set_error(FQTK_EINVAL, "adapter " + std::to_string(k) + " is not plain ACGT");
+        }
+        if (a.size() < min_overlap || a.size() > kAdapterMaxLen)
+            return set_error(FQTK_EINVAL, "adapter " + std::to_string(k) + " has " + std::to_string(a.size()) + " bases: its length is from min_overlap to 64");
+        if (a.size() * max_error_pct / 100u > kAdapterMaxErrors)
+            return set_error(FQTK_EINVAL, "max_error_pct allows adapter " + std::to_string(k) + " more than 7 mismatches: floor(length * max_error_pct / 100) is at most 7");
+        seqs.push_back(a);
+    }
+    for (uint32_t j = 0; j < A.n_ain; ++j) {
+        const std::string &a = seqs[std::min<size_t>(j, seqs.size() - 1)];
+        const uint32_t m = (uint32_t)a.size();
+        for (uint32_t k = 0; k < m; ++k) {
+            const uint32_t b = a[k] == 'A' ? 0u : a[k] == 'C' ? 1u : a[k] == 'G' ? 2u : 3u;
+            (k < 32u ? A.base_lo[j][b] : A.base_hi[j][b]) |= 1u << (k & 31u);
+        }
+        A.e_max[j] = (uint8_t)(m * max_error_pct / 100u);
+        for (uint32_t t = 0; t <= A.e_max[j]; ++t) {   // ov_t: allowed() does not decrease with the overlap, and m itself allows e_max
+            uint32_t ov = min_overlap;
+            while (ov * max_error_pct / 100u < t) ++ov;
+            A.ov[j][t] = (uint8_t)ov;
+        }
+    }
+    {
+        const char *e = std::getenv("FQTK_ADAPTER_GRID");
+        d->adapt_grid = e && *e ? (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 10), 1u << 16) : 0u;
+    }
+    if (A.n_ain) {   // (no scanned input: zero row words, no table, no kernel)
+        DX_TRY(hipSetDevice(d->device));
+        const size_t bytes = ((size_t)A.n_samples + 1) * A.row_words * sizeof(unsigned long long);
+        DX_TRY(hipMalloc(reinterpret_cast<void **>(&d->d_adapt), bytes));
+        DX_TRY(hipMemset(d->d_adapt, 0, bytes));
+    }
+    d->A = A;
+    d->adapters = true;
+    return FQTK_OK;
+}
+
+uint32_t fqtk_demuxer_adapter_row_words(const fqtk_demuxer *d) {
+    if (!d) return 0u;
+    uint32_t n_ain = 0;
+    for (size_t q = 0; q < d->t_segs.size(); ++q)
+        if (q == 0 || d->t_seg_input[q] != d->t_seg_input[q - 1]) ++n_ain;
+    return kAdapterRowWords * n_ain;
+}
+
+int fqtk_demuxer_adapter(fqtk_demuxer *d, uint64_t *out) {
+    if (!d) return set_error(FQTK_EINVAL, "NULL argument");
+    if (!d->adapters) return set_error(FQTK_EINVAL, "the adapter scan was not enabled (fqtk_demuxer_adapter_enable)");
+    if (!d->A.n_ain) return FQTK_OK;   // (zero row words: nothing to add, whatever `out` is)
+    if (!out) return set_error(FQTK_EINVAL, "NULL argument");
+    DX_TRY(hipSetDevice(d->device));
+    DX_TRY(hipStreamSynchronize(d->s_a));
+    std::vector<unsigned long long> h(((size_t)d->C.n_samples + 1) * d->A.row_words);
+    DX_TRY(hipMemcpy(h.data(), d->d_adapt, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < h.size(); ++i) out[i] += (uint64_t)h[i];
     return FQTK_OK;
 }

@@ -50,6 +50,7 @@
 #include "header.hpp"
 #include "metrics.hpp"
 #include "quality.hpp"
+#include "adapters.hpp"
 #include "read_structure.hpp"
 #include "region_inflate.hpp"
 #include "samples.hpp"
@@ -202,6 +203,9 @@ struct Options {
     bool index_pairs = false;        // --index-pairs: index-1 x index-2 tally of the unmatched templates on the device -> index-pairs.txt
     uint32_t pairs_len_a = 0;        //   length of the first of the two sample-barcode segments (main() works it out before any input is opened)
     bool quality_metrics = false;    // --quality-metrics: per-sample yield and quality in demux-quality-metrics.txt
+    std::vector<std::string> adapters;   // --adapter-metrics SEQ1[,SEQ2]: 3' adapter scan of the template reads on the device -> adapter-metrics.txt
+    unsigned long adapter_rule[3] = {5, 10, 30};   //   --adapter-rule MINOVERLAP,ERRPCT,SHORT
+    bool adapter_rule_given = false;
     bool weighted = false;           // --quality-weighted MAXCOST,DELTA: a mismatch costs the base's quality (fqtk_demuxer_weighted_enable)
     unsigned long max_cost = 0, min_cost_delta = 0;
     bool mismatch_flags_given = false;   //   --max-mismatches / --min-mismatch-delta were given: ignored with --quality-weighted, and said so
@@ -247,6 +251,16 @@ const char *kUsage =
     "      --quality-metrics                       tally yield and quality per sample and read over the template segments -- templates, perfect and\n"
     "                                              one-mismatch barcode matches, bases, bases at or above Q20 / Q30, mean quality -- and write\n"
     "                                              <OUTPUT>/demux-quality-metrics.txt; on the device unless --host-output (additive flag)\n"
+    "      --adapter-metrics <SEQ1[,SEQ2]>         scan the template reads for a 3' adapter on the device and write <OUTPUT>/adapter-metrics.txt: per sample\n"
+    "                                              and read the reads scanned, those that run into the adapter, the bases that costs, the inserts shorter\n"
+    "                                              than SHORT, and the reads over 512 bases, which are not scanned.  The j-th input that has a template\n"
+    "                                              segment is scanned over its last T segment for SEQj (the last SEQ when there are fewer); plain ACGT,\n"
+    "                                              at most 64 bases.  An offset p of a read of n bases is a hit when, over ov = min(length, n - p) bases,\n"
+    "                                              ov >= MINOVERLAP and the mismatches are at most floor(ov * ERRPCT / 100) -- N, '.', IUPAC codes never\n"
+    "                                              match, lower case does; the smallest hit counts.  Records are not trimmed.  Works with every other\n"
+    "                                              report and assignment flag; not with --host-output (additive flag)\n"
+    "      --adapter-rule <MINOVERLAP,ERRPCT,SHORT> the rule of --adapter-metrics [default: 5,10,30]: MINOVERLAP from 1 to the adapters' length, ERRPCT\n"
+    "                                              0..30 with floor(length * ERRPCT / 100) <= 7 (additive flag)\n"
     "      --index-pairs                           assign each of the two sample-barcode segments of the unmatched templates on its own\n"
     "                                              (--max-mismatches and --min-mismatch-delta per index) against the sample sheet's distinct\n"
     "                                              indexes, on the device, and write the pairs and their templates to <OUTPUT>/index-pairs.txt\n"
@@ -385,6 +399,16 @@ Options parse_args(int argc, char **argv) {
         else if (a == "--top-unmatched") num(&o.top_unmatched);
         else if (a == "--index-pairs") o.index_pairs = true;
         else if (a == "--quality-metrics") o.quality_metrics = true;
+        else if (a == "--adapter-metrics") {
+            const std::string v = single();
+            o.adapters.clear();
+            if (!parse_adapter_list(v, &o.adapters)) die("invalid value '" + v + "' for '--adapter-metrics': expected SEQ1[,SEQ2..] (adapter sequences, comma-separated)");
+        }
+        else if (a == "--adapter-rule") {
+            const std::string v = single();
+            if (!parse_adapter_rule(v, o.adapter_rule)) die("invalid value '" + v + "' for '--adapter-rule': expected MINOVERLAP,ERRPCT,SHORT (three non-negative integers)");
+            o.adapter_rule_given = true;
+        }
         else if (a == "--help" || a == "-h") { std::fputs(kUsage, stdout); std::exit(0); }
         else die("unexpected argument '" + a + "' found\n\n" + kUsage);
     }
@@ -778,6 +802,23 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
     if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
 }
 
+// --adapter-metrics: the table (summed over devices) as adapter-metrics.txt
+void write_adapter_metrics(const Options &opt, const std::vector<Sample> &samples, const AdapterTable &table) {
+    std::vector<std::string> ids, barcodes;
+    for (const Sample &s : samples) { ids.push_back(s.sample_id); barcodes.push_back(s.barcode); }
+    ids.push_back(opt.unmatched_prefix);
+    barcodes.push_back(".");
+    const std::string path = opt.output + "/adapter-metrics.txt", text = adapter_tsv(table, ids, barcodes);
+    {
+        std::lock_guard<std::mutex> lk(g_created_mu);
+        g_created.push_back(path);
+    }
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) die("cannot create " + path + ": " + std::strerror(errno));
+    write_all(fd, reinterpret_cast<const uint8_t *>(text.data()), text.size(), path);
+    if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
+}
+
 [[noreturn]] void run_gpu_output(const Options &opt, const Plan &plan, const std::vector<Sample> &samples,
                                  std::vector<std::unique_ptr<FastqSource>> &sources, bool skip_few) {
     const size_t n_inputs = plan.rs.size(), S = samples.size(), G = opt.devices.size();
@@ -899,6 +940,13 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
             cfg.compression_level = (int)opt.compression_level;
             if (fqtk_demuxer_create(matchers[g], &cfg, &demuxers[g]) != FQTK_OK) die(std::string("cannot set up the GPU record pipeline: ") + fqtk_last_error());
             if (opt.quality_metrics && fqtk_demuxer_quality_enable(demuxers[g]) != FQTK_OK) die(std::string("cannot set up the quality metrics: ") + fqtk_last_error());
+            if (!opt.adapters.empty()) {
+                std::vector<const char *> seqs;
+                for (const std::string &a : opt.adapters) seqs.push_back(a.c_str());
+                if (fqtk_demuxer_adapter_enable(demuxers[g], seqs.data(), (uint32_t)seqs.size(), (uint32_t)opt.adapter_rule[0], (uint32_t)opt.adapter_rule[1],
+                                                (uint32_t)opt.adapter_rule[2]) != FQTK_OK)
+                    die(std::string("invalid use of '--adapter-metrics': ") + fqtk_last_error());
+            }
             if (opt.weighted && fqtk_demuxer_weighted_enable(demuxers[g], (uint32_t)opt.max_cost, (uint32_t)opt.min_cost_delta) != FQTK_OK)
                 die(std::string("cannot set up quality-weighted assignment: ") + fqtk_last_error());
             if (opt.per_index && fqtk_demuxer_per_index_enable(demuxers[g], (uint32_t)opt.per_index_mm[0], (uint32_t)opt.min_mismatch_delta,
@@ -1753,6 +1801,17 @@ void write_quality_metrics(const Options &opt, const Plan &plan, const std::vect
             if (qt.row(s)[0] != counts[s]) die("internal error: the quality metrics' template counts differ from the per-sample counts");
         write_quality_metrics(opt, plan, samples, qt);
     }
+    if (!opt.adapters.empty()) {   // the devices' tables, summed (fqtk_demuxer_adapter ADDS)
+        AdapterTable at;
+        at.init(S, scanned_inputs(plan.rs));
+        if (at.row_words != fqtk_demuxer_adapter_row_words(demuxers[0])) die("internal error: the adapter metrics' row differs from the read structures'");
+        for (size_t g = 0; g < G; ++g)
+            if (fqtk_demuxer_adapter(demuxers[g], at.v.data()) != FQTK_OK) die(fqtk_last_error());
+        for (size_t s = 0; s <= S; ++s)
+            for (size_t j = 0; j < at.n_scanned; ++j)
+                if (at.row(s)[5 * j] + at.row(s)[5 * j + 4] != counts[s]) die("internal error: the adapter metrics' read counts differ from the per-sample counts");
+        write_adapter_metrics(opt, samples, at);
+    }
     if (!write_metrics_tsv(opt.output + "/demux-metrics.txt", rows, &err)) die(err);
     end_process();
 }
@@ -1893,6 +1952,10 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "Note: --max-mismatches is ignored with --per-index-mismatches (%lu,%lu decide; --min-mismatch-delta %lu is each index's delta).\n",
                          opt.per_index_mm[0], opt.per_index_mm[1], opt.min_mismatch_delta);
     }
+    if (opt.adapter_rule_given && opt.adapters.empty()) die("invalid use of '--adapter-rule' without '--adapter-metrics': it is the rule of that scan and of nothing else");
+    if (!opt.adapters.empty() && (opt.host_output || env_on("FQTK_HOST_OUTPUT")))
+        die("invalid use of '--adapter-metrics' with '--host-output': the host routers hold no text of the reads on the device; "
+            "the adapter scan runs in the GPU record pipeline only");
     if (opt.weighted) {   // what the weighted rule does not take: said here, before any input is opened
         if (opt.host_output || env_on("FQTK_HOST_OUTPUT"))
             die("invalid use of '--quality-weighted' with '--host-output': the host routers carry no quality rows of the sample barcodes; "
@@ -1996,6 +2059,8 @@ int main(int argc, char **argv) {
             die("invalid use of '--quality-weighted': the GPU record pipeline does not take this configuration (" + why + "), and the host routers carry no quality rows");
         if (opt.per_index)
             die("invalid use of '--per-index-mismatches': the GPU record pipeline does not take this configuration (" + why + "), and the host routers match whole barcodes");
+        if (!opt.adapters.empty())
+            die("invalid use of '--adapter-metrics': the GPU record pipeline does not take this configuration (" + why + "), and the host routers hold no text on the device");
         info("The GPU record pipeline does not take this configuration (%s): records are formatted and compressed on the host.", why.c_str());
     }
     const size_t G = opt.devices.size();

@@ -230,6 +230,19 @@ class Demuxer:
         _check(self._lib.fqtk_demuxer_quality(self._h, q.ctypes.data))
         return q
 
+    def enable_adapters(self, adapters: Sequence[str], min_overlap: int = 5, max_error_pct: int = 10, short_insert: int = 30) -> None:
+        """3' adapter scan of every chunk's template reads (before the first submit): the j-th input that has a T segment is scanned
+        over its last T segment for adapters[min(j, len - 1)]; the rule is stated in include/fqtk_demux.h."""
+        arr = (C.c_char_p * max(len(adapters), 1))(*[a.encode() for a in adapters])
+        _check(self._lib.fqtk_demuxer_adapter_enable(self._h, arr, len(adapters), int(min_overlap), int(max_error_pct), int(short_insert)))
+
+    def adapters(self) -> np.ndarray:
+        """[n_samples + 1, 5 * scanned inputs] uint64: per scanned input scanned, with_adapter, adapter_bases, short_inserts,
+        too_long (include/fqtk_demux.h); unmatched last."""
+        a = np.zeros((self.matcher.n_samples + 1, int(self._lib.fqtk_demuxer_adapter_row_words(self._h))), dtype=np.uint64)
+        _check(self._lib.fqtk_demuxer_adapter(self._h, a.ctypes.data))
+        return a
+
     def stage_seconds(self) -> Dict[str, float]:
         s = (C.c_double * _lib.FQTK_DEMUX_STAGES)()
         _check(self._lib.fqtk_demuxer_stage_seconds(self._h, s))

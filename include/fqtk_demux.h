@@ -268,6 +268,30 @@ uint32_t fqtk_demuxer_quality_row_words(const fqtk_demuxer *d);    /* 3 + 4 * n_
 /* Adds the (n_samples + 1) rows of all collected chunks into out (so several devices sum); FQTK_EINVAL when not enabled. */
 int fqtk_demuxer_quality(fqtk_demuxer *d, uint64_t *out);
 
+/* ---- 3' adapter read-through scan of the template reads, per-sample adapter metrics on the device (opt-in) ------------------------
+ * Parameters: adapters A_0 .. A_{k-1}, 1 <= k <= the number of scanned inputs (k = 1 where there is none), each plain ACGT (either
+ * case, stored upper case) of length m with min_overlap <= m <= 64; min_overlap >= 1; max_error_pct in 0..30 such that
+ * floor(m * max_error_pct / 100) <= 7 for every adapter; short_insert >= 0.  Anything else is FQTK_EINVAL and fqtk_last_error()
+ * says which parameter; so is enabling after the first submit, or twice.
+ * A SCANNED INPUT is an input whose read structure has a template (T) segment.  The j-th scanned input uses adapter
+ * A_min(j, k-1); its scanned span is the span of its LAST T segment -- the bytes the T file of that segment gets, a trailing
+ * '\r' excluded.  For a template that is not dropped, s = its sample (unmatched -> n_samples) and R[0..n) the span's sequence bytes:
+ *   n > 512: too_long += 1 for (s, input); the read is not scanned.  Otherwise scanned += 1, and for an offset p in [0, n):
+ *     ov = min(m, n - p)
+ *     mis(p) = #{ j < ov : (R[p+j] & 0xDF) != A[j] }     -- N, '.', IUPAC codes and junk bytes never match, lower case does
+ *     p is a hit iff ov >= min_overlap and mis(p) <= floor(ov * max_error_pct / 100)
+ *   The trim position is the SMALLEST hit p.  If there is one: with_adapter += 1, adapter_bases += n - p,
+ *   short_inserts += (p < short_insert).
+ * A row is 5 counters per scanned input, in input order: [scanned, with_adapter, adapter_bases, short_inserts, too_long];
+ * n_samples + 1 rows, unmatched last, kept across chunks.  scanned + too_long equals fqtk_demuxer_counts.  Exact integers.
+ * Records are not changed: the scan only reports (csrc/adapter_kernels.hip.h).  Not enabled: no kernel runs, nothing is
+ * allocated; no scanned input: zero row words, no kernel either. */
+int fqtk_demuxer_adapter_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap,
+                                uint32_t max_error_pct, uint32_t short_insert);
+uint32_t fqtk_demuxer_adapter_row_words(const fqtk_demuxer *d);    /* 5 * scanned inputs */
+/* Adds the (n_samples + 1) rows of all collected chunks into out (so several devices sum); FQTK_EINVAL when not enabled. */
+int fqtk_demuxer_adapter(fqtk_demuxer *d, uint64_t *out);
+
 /* Seconds of device time per stage, summed over the chunks collected so far (names: fqtk_demuxer_stage_name). */
 #define FQTK_DEMUX_STAGES 8
 int fqtk_demuxer_stage_seconds(fqtk_demuxer *d, double *seconds /* FQTK_DEMUX_STAGES */);
