@@ -189,6 +189,9 @@ SIGNATURES = [
     ("fqtk_demuxer_adapter_enable", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("fqtk_demuxer_adapter_row_words", C.c_uint32, [C.c_void_p]),
     ("fqtk_demuxer_adapter", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fqtk_demuxer_trim_enable", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("fqtk_demuxer_trim_row_words", C.c_uint32, [C.c_void_p]),
+    ("fqtk_demuxer_trim", C.c_int, [C.c_void_p, C.c_void_p]),
     ("fqtk_demuxer_stage_seconds", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("fqtk_demuxer_stage_name", C.c_char_p, [C.c_int]),
     ("fqtk_demuxer_feed", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),

@@ -141,6 +141,74 @@ __device__ __forceinline__ AdapterItem adapter_item(const TextSet &T, const Adap
     return it;
 }
 
+// The scan of one item by its group of 16 lanes (k_adapter; k_trim of trim_kernels.hip.h on a span that ends at its quality cut): the smallest hit
+// p of R[0..n_span), R[0] at byte `start` of scanned input j's text, 1 <= n_span <= kAdapterMaxSpan, in every lane of the group; 0xFFFFFFFF: no hit.
+// `planes`: the group's kAdapterGroupWords of LDS.  j is wave-uniform.
+__device__ __forceinline__ uint32_t adapter_scan(const TextSet &T, const AdapterConfig &A, uint32_t j, uint32_t *planes, uint32_t lane, uint32_t start, uint32_t n_span) {
+    const uint32_t in = A.ain[j];
+    const uint8_t *text = T.text[in];
+    const uint32_t len = T.len[in], lead = T.lead[in];
+    const uint32_t a0 = start & ~15u, sh = start & 15u, end = start + n_span;
+    // ---- load and encode: halfword (pass * 16 + lane) of every plane, aligned coordinates
+    __builtin_amdgcn_wave_barrier();   // (the round before has read its planes)
+    typedef uint16_t __attribute__((may_alias)) half_t;   // (halfword stores into planes that are read back as dwords)
+    half_t *half = reinterpret_cast<half_t *>(planes);
+#pragma unroll
+    for (uint32_t p = 0; p < kAdapterPasses; ++p) {
+        if (a0 + p * 256u >= end) break;   // (the group as one; what an earlier item left in the halfwords of such a pass lies at and beyond n: V masks it)
+        const uint32_t off = a0 + p * 256u + lane * 16u;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (off < end) v = tile_bytes(text, len, off / kLineTile, (off % kLineTile) / 16u, lead);
+        const uint32_t h = p * 16u + lane;
+        half[0u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'A');
+        half[1u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'C');
+        half[2u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'G');
+        half[3u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'T');
+    }
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    // ---- words lane, lane + 1, lane + 2 of V and of the planes, read coordinates (bit 0 = R[0])
+    uint32_t V[3], P[4][3];
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k) V[k] = low_bits((int32_t)n_span - (int32_t)(32u * (lane + k)));
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; ++b) {
+        const uint32_t *pl = planes + b * kAdapterPlaneWords + lane;
+        const uint32_t d0 = pl[0], d1 = pl[1], d2 = pl[2], d3 = pl[3];
+        P[b][0] = __builtin_amdgcn_alignbit(d1, d0, sh) & V[0];
+        P[b][1] = __builtin_amdgcn_alignbit(d2, d1, sh) & V[1];
+        P[b][2] = __builtin_amdgcn_alignbit(d3, d2, sh) & V[2];
+    }
+    // ---- scan: one step per base of the adapter, 32 offsets a lane
+    SlicedCount cnt;
+    cnt.c0 = cnt.c1 = cnt.c2 = cnt.ovf = 0u;
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; ++b) {
+        uint32_t mlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.base_lo[j][b]);
+        while (mlo) {   // shifts 0..31: words lane, lane + 1
+            const uint32_t q = (uint32_t)__builtin_ctz(mlo);
+            mlo &= mlo - 1u;
+            const uint32_t eq = __builtin_amdgcn_alignbit(P[b][1], P[b][0], q);
+            sliced_add(cnt, __builtin_amdgcn_alignbit(V[1], V[0], q) & ~eq);
+        }
+        uint32_t mhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.base_hi[j][b]);
+        while (mhi) {   // shifts 32..63: words lane + 1, lane + 2
+            const uint32_t q = (uint32_t)__builtin_ctz(mhi);
+            mhi &= mhi - 1u;
+            const uint32_t eq = __builtin_amdgcn_alignbit(P[b][2], P[b][1], q);
+            sliced_add(cnt, __builtin_amdgcn_alignbit(V[2], V[1], q) & ~eq);
+        }
+    }
+    // ---- decision: OR over t of (count == t) & (p <= n - ov_t)
+    const uint32_t e_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.e_max[j]);
+    uint32_t hit = 0;
+    for (uint32_t t = 0; t <= e_max; ++t) {
+        const uint32_t is_t = ~cnt.ovf & ((t & 1u) ? cnt.c0 : ~cnt.c0) & ((t & 2u) ? cnt.c1 : ~cnt.c1) & ((t & 4u) ? cnt.c2 : ~cnt.c2);
+        hit |= is_t & low_bits((int32_t)n_span - (int32_t)A.ov[j][t] + 1 - (int32_t)(32u * lane));
+    }
+    return row_min(hit ? 32u * lane + (uint32_t)__builtin_ctz(hit) : 0xFFFFFFFFu);
+}
+
 __global__ __launch_bounds__(kAdapterBlock) void k_adapter(TextSet T, AdapterConfig A, uint32_t n, const uint32_t *res, const uint8_t *skip,
                                                            unsigned long long *table, uint32_t n_counters, uint32_t use_lds, const ChunkStatus *st) {
     if (no_records(st)) return;
@@ -171,70 +239,7 @@ __global__ __launch_bounds__(kAdapterBlock) void k_adapter(TextSet T, AdapterCon
         if (it.live) {
             const uint32_t n_span = it.n;
             uint32_t trim = 0xFFFFFFFFu;
-            if (n_span <= kAdapterMaxSpan && n_span) {
-                const uint32_t in = A.ain[j];
-                const uint8_t *text = T.text[in];
-                const uint32_t len = T.len[in], lead = T.lead[in];
-                const uint32_t a0 = it.start & ~15u, sh = it.start & 15u, end = it.start + n_span;
-                // ---- load and encode: halfword (pass * 16 + lane) of every plane, aligned coordinates
-                __builtin_amdgcn_wave_barrier();   // (the round before has read its planes)
-                typedef uint16_t __attribute__((may_alias)) half_t;   // (halfword stores into planes that are read back as dwords)
-                half_t *half = reinterpret_cast<half_t *>(planes);
-#pragma unroll
-                for (uint32_t p = 0; p < kAdapterPasses; ++p) {
-                    if (a0 + p * 256u >= end) break;   // (the group as one; what an earlier item left in the halfwords of such a pass lies at and beyond n: V masks it)
-                    const uint32_t off = a0 + p * 256u + lane * 16u;
-                    uint4 v = make_uint4(0, 0, 0, 0);
-                    if (off < end) v = tile_bytes(text, len, off / kLineTile, (off % kLineTile) / 16u, lead);
-                    const uint32_t h = p * 16u + lane;
-                    half[0u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'A');
-                    half[1u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'C');
-                    half[2u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'G');
-                    half[3u * 2u * kAdapterPlaneWords + h] = (uint16_t)base_fragment(v, 'T');
-                }
-                __threadfence_block();
-                __builtin_amdgcn_wave_barrier();
-                // ---- words lane, lane + 1, lane + 2 of V and of the planes, read coordinates (bit 0 = R[0])
-                uint32_t V[3], P[4][3];
-#pragma unroll
-                for (uint32_t k = 0; k < 3u; ++k) V[k] = low_bits((int32_t)n_span - (int32_t)(32u * (lane + k)));
-#pragma unroll
-                for (uint32_t b = 0; b < 4u; ++b) {
-                    const uint32_t *pl = planes + b * kAdapterPlaneWords + lane;
-                    const uint32_t d0 = pl[0], d1 = pl[1], d2 = pl[2], d3 = pl[3];
-                    P[b][0] = __builtin_amdgcn_alignbit(d1, d0, sh) & V[0];
-                    P[b][1] = __builtin_amdgcn_alignbit(d2, d1, sh) & V[1];
-                    P[b][2] = __builtin_amdgcn_alignbit(d3, d2, sh) & V[2];
-                }
-                // ---- scan: one step per base of the adapter, 32 offsets a lane
-                SlicedCount cnt;
-                cnt.c0 = cnt.c1 = cnt.c2 = cnt.ovf = 0u;
-#pragma unroll
-                for (uint32_t b = 0; b < 4u; ++b) {
-                    uint32_t mlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.base_lo[j][b]);
-                    while (mlo) {   // shifts 0..31: words lane, lane + 1
-                        const uint32_t q = (uint32_t)__builtin_ctz(mlo);
-                        mlo &= mlo - 1u;
-                        const uint32_t eq = __builtin_amdgcn_alignbit(P[b][1], P[b][0], q);
-                        sliced_add(cnt, __builtin_amdgcn_alignbit(V[1], V[0], q) & ~eq);
-                    }
-                    uint32_t mhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.base_hi[j][b]);
-                    while (mhi) {   // shifts 32..63: words lane + 1, lane + 2
-                        const uint32_t q = (uint32_t)__builtin_ctz(mhi);
-                        mhi &= mhi - 1u;
-                        const uint32_t eq = __builtin_amdgcn_alignbit(P[b][2], P[b][1], q);
-                        sliced_add(cnt, __builtin_amdgcn_alignbit(V[2], V[1], q) & ~eq);
-                    }
-                }
-                // ---- decision: OR over t of (count == t) & (p <= n - ov_t)
-                const uint32_t e_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)A.e_max[j]);
-                uint32_t hit = 0;
-                for (uint32_t t = 0; t <= e_max; ++t) {
-                    const uint32_t is_t = ~cnt.ovf & ((t & 1u) ? cnt.c0 : ~cnt.c0) & ((t & 2u) ? cnt.c1 : ~cnt.c1) & ((t & 4u) ? cnt.c2 : ~cnt.c2);
-                    hit |= is_t & low_bits((int32_t)n_span - (int32_t)A.ov[j][t] + 1 - (int32_t)(32u * lane));
-                }
-                trim = row_min(hit ? 32u * lane + (uint32_t)__builtin_ctz(hit) : 0xFFFFFFFFu);
-            }
+            if (n_span <= kAdapterMaxSpan && n_span) trim = adapter_scan(T, A, j, planes, lane, it.start, n_span);
             // ---- tally: lane 0 scanned, 1 with_adapter, 2 adapter_bases, 3 short_inserts, 4 too_long
             const bool too_long = n_span > kAdapterMaxSpan, found = trim != 0xFFFFFFFFu;
             const uint32_t add = lane == 0u ? (too_long ? 0u : 1u) : lane == 1u ? (found ? 1u : 0u) : lane == 2u ? (found ? n_span - trim : 0u)

@@ -31,6 +31,7 @@
 #include "matcher_internal.hpp"
 #include "quality_kernels.hip.h"
 #include "adapter_kernels.hip.h"
+#include "trim_kernels.hip.h"
 
 namespace {
 using namespace fqtk::demux;
@@ -206,6 +207,12 @@ struct fqtk_demuxer {
     AdapterConfig A{};
     unsigned long long *d_adapt = nullptr;  // [n_samples + 1][A.row_words]
     uint32_t adapt_grid = 0;                // FQTK_ADAPTER_GRID=k, as qual_grid
+    // 3' quality and adapter trimming of the template reads (fqtk_demuxer_trim_enable): level 2 of trim_kernels.hip.h
+    bool trim = false;
+    TrimConfig R{};
+    unsigned long long *d_trim = nullptr;   // [n_samples + 1][R.A.row_words]
+    uint32_t trim_grid = 0;                 // FQTK_TRIM_GRID=k, as qual_grid
+    fqtk_demux_segment last_seg[FQTK_DEMUX_MAX_INPUTS] = {};   // the last segment of every input's read structure as configured
     bool weighted = false;                  // quality-weighted assignment (fqtk_demuxer_weighted_enable)
     bool per_index = false;                 // per-index mismatch budgets (fqtk_demuxer_per_index_enable)
     std::vector<fqtk_demux_segment> t_segs; // the T segments of all inputs as configured, in input order, wanted as files or not
@@ -367,6 +374,7 @@ int fqtk_demuxer_create(fqtk_matcher *m, const fqtk_demux_config *cfg, fqtk_demu
         for (uint32_t k = 0; k < cfg->n_segments[i]; ++k, ++at) {
             const fqtk_demux_segment &sg = cfg->segments[at];
             min_len += sg.length >= 0 ? (uint32_t)sg.length : 1u;   // demux.rs:298
+            if (k + 1 == cfg->n_segments[i]) d->last_seg[i] = sg;
             if (sg.length < 0 && k + 1 != cfg->n_segments[i]) { delete d; return set_error(FQTK_EINVAL, "only the last segment of a read structure may be '+'"); }
             int ty = -1;
             for (int q = 0; q < 4; ++q) if (sg.kind == kKinds[q]) ty = q;
@@ -479,6 +487,7 @@ void fqtk_demuxer_destroy(fqtk_demuxer *d) {
     if (d->d_counts) (void)hipFree(d->d_counts);
     if (d->d_qual) (void)hipFree(d->d_qual);
     if (d->d_adapt) (void)hipFree(d->d_adapt);
+    if (d->d_trim) (void)hipFree(d->d_trim);
     if (d->d_tok) (void)hipFree(d->d_tok);
     for (hipStream_t st : {d->s_in, d->s_a, d->s_b, d->s_out}) if (st) (void)hipStreamDestroy(st);
     delete d;
@@ -491,6 +500,18 @@ namespace {
 //  text buffer first, base being where it lies there)
 struct Window { const uint8_t *base; uint32_t lead, first_line; const uint8_t *copy_from; int copy_dev; };
 }
+// The adapter scan of a chunk on stream A (it reads the window's text and the record views; the matcher's results are behind it on that stream).
+static int launch_adapter_scan(fqtk_demuxer *d, Slot &s, const TextSet &T, uint32_t n) {
+    const uint32_t items = ((n + 3u) & ~3u) * d->A.n_ain;
+    const uint32_t n_counters = (d->C.n_samples + 1u) * d->A.row_words;
+    const uint32_t use_lds = n_counters <= kQualLdsCounters ? 1u : 0u;
+    const uint32_t grid = std::min<uint32_t>((items + kAdapterGroups - 1u) / kAdapterGroups, d->adapt_grid ? d->adapt_grid : (uint32_t)d->num_cus * 8u);
+    hipLaunchKernelGGL(k_adapter, dim3(grid), dim3(kAdapterBlock), (kAdapterGroups * kAdapterGroupWords + (use_lds ? n_counters : 0u)) * sizeof(uint32_t), d->s_a, T, d->A, n,
+                       (const uint32_t *)s.res.p, (const uint8_t *)s.skip.p, d->d_adapt, n_counters, use_lds, (const ChunkStatus *)s.d_status);
+    DX_TRY(hipGetLastError());
+    return FQTK_OK;
+}
+
 // One chunk: `text` (host buffers, copied in) or `win` (text already on the device).
 static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, const uint64_t *text_len, const Window *win, uint32_t n) {
     if (slot < 0 || slot >= FQTK_DEMUX_SLOTS) return set_error(FQTK_EINVAL, "slot out of range");
@@ -607,6 +628,16 @@ static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, 
     } else if ((rc = fqtk_matcher_assign_batch_device(d->m, s.obs.p, stride, C.use_lens ? s.lens.p : nullptr, n, s.res.p, nullptr, A)) != FQTK_OK) return rc;
     if ((rc = fqtk::internal::take_device_error(d->m, A, &s.d_status->matcher_err)) != FQTK_OK) return rc;
     DX_TRY(hipEventRecord(s.ev[2], A));
+    if (d->trim) {   // shortens seq_len of the trimmed inputs' records: everything from here on sees the trimmed reads
+        if (d->adapters && d->A.n_ain && (rc = launch_adapter_scan(d, s, T, n)) != FQTK_OK) return rc;   // (the adapter metrics report on the reads as they came in)
+        const uint32_t items = ((n + 3u) & ~3u) * d->R.A.n_ain;
+        const uint32_t n_counters = (C.n_samples + 1u) * d->R.A.row_words;
+        const uint32_t use_lds = n_counters <= kQualLdsCounters ? 1u : 0u;
+        const uint32_t grid = std::min<uint32_t>((items + kAdapterGroups - 1u) / kAdapterGroups, d->trim_grid ? d->trim_grid : (uint32_t)d->num_cus * 8u);
+        hipLaunchKernelGGL(k_trim, dim3(grid), dim3(kAdapterBlock), (kAdapterGroups * kTrimGroupWords + (use_lds ? n_counters : 0u)) * sizeof(uint32_t), A, T, d->R, n,
+                           (const uint32_t *)s.res.p, (const uint8_t *)s.skip.p, d->d_trim, n_counters, use_lds, (const ChunkStatus *)s.d_status);
+        DX_TRY(hipGetLastError());
+    }
     DX_TRY(hipMemsetAsync(s.tile_tot.p, 0, (size_t)n_tiles * d->cols * sizeof(uint32_t), A));
     hipLaunchKernelGGL(k_plan_rank, dim3(n_tiles), dim3(kTile), 0, A, T, C, n, s.res.p, s.skip.p, s.plans.p, s.rec_off.p, s.tile_tot.p, s.d_status);
     DX_TRY(hipGetLastError());
@@ -630,15 +661,7 @@ static int submit_common(fqtk_demuxer *d, int slot, const uint8_t *const *text, 
                            (const uint8_t *)s.skip.p, d->d_qual, n_counters, use_lds, (const ChunkStatus *)s.d_status);
         DX_TRY(hipGetLastError());
     }
-    if (d->adapters && d->A.n_ain) {   // (before ev_fmt as well: it reads the window's text; the matcher's results are behind it on this stream)
-        const uint32_t items = ((n + 3u) & ~3u) * d->A.n_ain;
-        const uint32_t n_counters = (C.n_samples + 1u) * d->A.row_words;
-        const uint32_t use_lds = n_counters <= kQualLdsCounters ? 1u : 0u;
-        const uint32_t grid = std::min<uint32_t>((items + kAdapterGroups - 1u) / kAdapterGroups, d->adapt_grid ? d->adapt_grid : (uint32_t)d->num_cus * 8u);
-        hipLaunchKernelGGL(k_adapter, dim3(grid), dim3(kAdapterBlock), (kAdapterGroups * kAdapterGroupWords + (use_lds ? n_counters : 0u)) * sizeof(uint32_t), A, T, d->A, n,
-                           (const uint32_t *)s.res.p, (const uint8_t *)s.skip.p, d->d_adapt, n_counters, use_lds, (const ChunkStatus *)s.d_status);
-        DX_TRY(hipGetLastError());
-    }
+    if (d->adapters && d->A.n_ain && !d->trim && (rc = launch_adapter_scan(d, s, T, n)) != FQTK_OK) return rc;   // (before ev_fmt as well: it reads the window's text)
     if (T.window) {   // (before ev_fmt: the arena the window lies in may be reused once that event is reached)
         hipLaunchKernelGGL(k_save_error_text, dim3(2 * C.n_inputs), dim3(64), 0, A, T, C.n_inputs, n, (const ChunkStatus *)s.d_status, s.d_err_text);
         DX_TRY(hipGetLastError());
@@ -1540,25 +1563,23 @@ int fqtk_demuxer_quality(fqtk_demuxer *d, uint64_t *out) {
     return FQTK_OK;
 }
 
-int fqtk_demuxer_adapter_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap, uint32_t max_error_pct, uint32_t short_insert) {
-    if (!d || !adapters) return set_error(FQTK_EINVAL, "NULL argument");
-    if (d->chunk_no) return set_error(FQTK_EINVAL, "the adapter scan is enabled before the first chunk is submitted");
-    if (d->adapters) return set_error(FQTK_EINVAL, "the adapter scan is enabled once");
-    AdapterConfig A;
-    std::memset(&A, 0, sizeof A);
-    A.n_samples = d->C.n_samples;
-    A.short_insert = short_insert;
-    for (size_t q = 0; q < d->t_segs.size(); ++q) {   // (t_segs is in input order: an input's last T segment overwrites its earlier ones)
+// The inputs that have a T segment, in input order, each with its LAST T segment (t_segs is in input order: a later one overwrites).
+static void scanned_inputs(const fqtk_demuxer *d, AdapterConfig &A) {
+    for (size_t q = 0; q < d->t_segs.size(); ++q) {
         const uint32_t i = d->t_seg_input[q];
         if (A.n_ain == 0 || A.ain[A.n_ain - 1u] != i) A.ain[A.n_ain++] = (uint8_t)i;
         A.t_off[A.n_ain - 1u] = d->t_segs[q].offset;
         A.t_len[A.n_ain - 1u] = d->t_segs[q].length;
     }
-    A.row_words = kAdapterRowWords * A.n_ain;
-    if (min_overlap == 0) return set_error(FQTK_EINVAL, "the adapter scan takes a min_overlap of 1 or more");
-    if (max_error_pct > 30) return set_error(FQTK_EINVAL, "the adapter scan takes a max_error_pct of 0 to 30");
+}
+
+// The adapters and the rule of a scan (`what`: "the adapter scan" / "trimming") into A, whose scanned inputs are in place: the masks of
+// the j-th scanned input's adapter A_min(j, k-1), its e_max and its ov_t (adapter_kernels.hip.h).
+static int adapter_rule_config(AdapterConfig &A, const std::string &what, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap, uint32_t max_error_pct) {
+    if (min_overlap == 0) return set_error(FQTK_EINVAL, what + " takes a min_overlap of 1 or more");
+    if (max_error_pct > 30) return set_error(FQTK_EINVAL, what + " takes a max_error_pct of 0 to 30");
     if (n_adapters == 0 || n_adapters > std::max<uint32_t>(A.n_ain, 1u))
-        return set_error(FQTK_EINVAL, "the adapter scan takes between 1 adapter and one per scanned input (an input with a template segment): n_adapters is " +
+        return set_error(FQTK_EINVAL, what + " takes between 1 adapter and one per scanned input (an input with a template segment): n_adapters is " +
                                           std::to_string(n_adapters) + ", scanned inputs " + std::to_string(A.n_ain));
     std::vector<std::string> seqs;
     for (uint32_t k = 0; k < n_adapters; ++k) {
@@ -1588,6 +1609,21 @@ int fqtk_demuxer_adapter_enable(fqtk_demuxer *d, const char *const *adapters, ui
             A.ov[j][t] = (uint8_t)ov;
         }
     }
+    return FQTK_OK;
+}
+
+int fqtk_demuxer_adapter_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap, uint32_t max_error_pct, uint32_t short_insert) {
+    if (!d || !adapters) return set_error(FQTK_EINVAL, "NULL argument");
+    if (d->chunk_no) return set_error(FQTK_EINVAL, "the adapter scan is enabled before the first chunk is submitted");
+    if (d->adapters) return set_error(FQTK_EINVAL, "the adapter scan is enabled once");
+    AdapterConfig A;
+    std::memset(&A, 0, sizeof A);
+    A.n_samples = d->C.n_samples;
+    A.short_insert = short_insert;
+    scanned_inputs(d, A);
+    A.row_words = kAdapterRowWords * A.n_ain;
+    const int rc = adapter_rule_config(A, "the adapter scan", adapters, n_adapters, min_overlap, max_error_pct);
+    if (rc != FQTK_OK) return rc;
     {
         const char *e = std::getenv("FQTK_ADAPTER_GRID");
         d->adapt_grid = e && *e ? (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 10), 1u << 16) : 0u;
@@ -1620,6 +1656,62 @@ int fqtk_demuxer_adapter(fqtk_demuxer *d, uint64_t *out) {
     DX_TRY(hipStreamSynchronize(d->s_a));
     std::vector<unsigned long long> h(((size_t)d->C.n_samples + 1) * d->A.row_words);
     DX_TRY(hipMemcpy(h.data(), d->d_adapt, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) out[i] += (uint64_t)h[i];
+    return FQTK_OK;
+}
+
+int fqtk_demuxer_trim_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap, uint32_t max_error_pct, uint32_t quality_cutoff,
+                             uint32_t min_length) {
+    if (!d || (n_adapters && !adapters)) return set_error(FQTK_EINVAL, "NULL argument");
+    if (d->chunk_no) return set_error(FQTK_EINVAL, "trimming is enabled before the first chunk is submitted");
+    if (d->trim) return set_error(FQTK_EINVAL, "trimming is enabled once");
+    if (quality_cutoff > kTrimMaxCutoff) return set_error(FQTK_EINVAL, "trimming takes a quality_cutoff of 0 to 93 (0: no quality trimming), not " + std::to_string(quality_cutoff));
+    if (min_length == 0) return set_error(FQTK_EINVAL, "trimming takes a min_length of 1 or more: a written read is never empty");
+    if (n_adapters == 0 && quality_cutoff == 0) return set_error(FQTK_EINVAL, "trimming has nothing to do: n_adapters is 0 and quality_cutoff is 0");
+    TrimConfig R;
+    std::memset(&R, 0, sizeof R);
+    AdapterConfig &A = R.A;
+    A.n_samples = d->C.n_samples;
+    scanned_inputs(d, A);
+    A.row_words = kTrimRowWords * A.n_ain;
+    if (A.n_ain == 0) return set_error(FQTK_EINVAL, "trimming takes an input with a template (T) segment: no read structure has one");
+    for (uint32_t j = 0; j < A.n_ain; ++j) {   // shrinking seq_len can only cut a read's tail
+        const fqtk_demux_segment &last = d->last_seg[A.ain[j]];
+        if (last.kind != 'T' || last.offset != A.t_off[j])
+            return set_error(FQTK_EINVAL, "trimming takes read structures whose last template (T) segment is their last segment: input " + std::to_string(A.ain[j]) +
+                                              " has a segment behind it");
+    }
+    if (n_adapters) {
+        const int rc = adapter_rule_config(A, "trimming", adapters, n_adapters, min_overlap, max_error_pct);
+        if (rc != FQTK_OK) return rc;
+    }
+    R.has_adapters = n_adapters ? 1u : 0u;
+    R.min_overlap = min_overlap;
+    R.cutoff33 = quality_cutoff ? quality_cutoff + 33u : 0u;
+    R.min_length = min_length;
+    {
+        const char *e = std::getenv("FQTK_TRIM_GRID");
+        d->trim_grid = e && *e ? (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 10), 1u << 16) : 0u;
+    }
+    DX_TRY(hipSetDevice(d->device));
+    const size_t bytes = ((size_t)A.n_samples + 1) * A.row_words * sizeof(unsigned long long);
+    DX_TRY(hipMalloc(reinterpret_cast<void **>(&d->d_trim), bytes));
+    DX_TRY(hipMemset(d->d_trim, 0, bytes));
+    d->R = R;
+    d->trim = true;
+    return FQTK_OK;
+}
+
+uint32_t fqtk_demuxer_trim_row_words(const fqtk_demuxer *d) { return fqtk_demuxer_adapter_row_words(d) / kAdapterRowWords * kTrimRowWords; }
+
+int fqtk_demuxer_trim(fqtk_demuxer *d, uint64_t *out) {
+    if (!d) return set_error(FQTK_EINVAL, "NULL argument");
+    if (!d->trim) return set_error(FQTK_EINVAL, "trimming was not enabled (fqtk_demuxer_trim_enable)");
+    if (!out) return set_error(FQTK_EINVAL, "NULL argument");
+    DX_TRY(hipSetDevice(d->device));
+    DX_TRY(hipStreamSynchronize(d->s_a));
+    std::vector<unsigned long long> h(((size_t)d->C.n_samples + 1) * d->R.A.row_words);
+    DX_TRY(hipMemcpy(h.data(), d->d_trim, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < h.size(); ++i) out[i] += (uint64_t)h[i];
     return FQTK_OK;
 }

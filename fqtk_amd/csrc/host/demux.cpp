@@ -51,6 +51,7 @@
 #include "metrics.hpp"
 #include "quality.hpp"
 #include "adapters.hpp"
+#include "trim.hpp"
 #include "read_structure.hpp"
 #include "region_inflate.hpp"
 #include "samples.hpp"
@@ -206,7 +207,13 @@ struct Options {
     std::vector<std::string> adapters;   // --adapter-metrics SEQ1[,SEQ2]: 3' adapter scan of the template reads on the device -> adapter-metrics.txt
     unsigned long adapter_rule[3] = {5, 10, 30};   //   --adapter-rule MINOVERLAP,ERRPCT,SHORT
     bool adapter_rule_given = false;
-    bool weighted = false;           // --quality-weighted MAXCOST,DELTA: a mismatch costs the base's quality (fqtk_demuxer_weighted_enable)
+    std::vector<std::string> trim_adapters;   // --trim-adapters SEQ1[,SEQ2]: cut the template reads at their 3' adapter on the device -> trim-metrics.txt
+    unsigned long trim_quality = 0;           // --trim-quality Q: cut their low-quality 3' tails (0: not)
+    unsigned long trim_rule[2] = {5, 10};     //   --trim-rule MINOVERLAP,ERRPCT
+    unsigned long trim_min_length = 1;        //   --trim-min-length N
+    bool trim_rule_given = false, trim_min_length_given = false;
+    bool trim() const { return !trim_adapters.empty() || trim_quality != 0; }
+    bool weighted = false;          // --quality-weighted MAXCOST,DELTA: a mismatch costs the base's quality (fqtk_demuxer_weighted_enable)
     unsigned long max_cost = 0, min_cost_delta = 0;
     bool mismatch_flags_given = false;   //   --max-mismatches / --min-mismatch-delta were given: ignored with --quality-weighted, and said so
     bool per_index = false;          // --per-index-mismatches M1,M2: each of the two sample-barcode segments has a budget of its own (fqtk_demuxer_per_index_enable)
@@ -257,10 +264,21 @@ const char *kUsage =
     "                                              segment is scanned over its last T segment for SEQj (the last SEQ when there are fewer); plain ACGT,\n"
     "                                              at most 64 bases.  An offset p of a read of n bases is a hit when, over ov = min(length, n - p) bases,\n"
     "                                              ov >= MINOVERLAP and the mismatches are at most floor(ov * ERRPCT / 100) -- N, '.', IUPAC codes never\n"
-    "                                              match, lower case does; the smallest hit counts.  Records are not trimmed.  Works with every other\n"
+    "                                              match, lower case does; the smallest hit counts.  This flag trims nothing (--trim-adapters does).  Works with every other\n"
     "                                              report and assignment flag; not with --host-output (additive flag)\n"
     "      --adapter-rule <MINOVERLAP,ERRPCT,SHORT> the rule of --adapter-metrics [default: 5,10,30]: MINOVERLAP from 1 to the adapters' length, ERRPCT\n"
     "                                              0..30 with floor(length * ERRPCT / 100) <= 7 (additive flag)\n"
+    "      --trim-adapters <SEQ1[,SEQ2]>           trim the template reads on the device before they are written: the j-th input that has a template\n"
+    "                                              segment is cut at the smallest hit of SEQj under the rule of --adapter-metrics (MINOVERLAP, ERRPCT\n"
+    "                                              from --trim-rule).  Its last T segment must be the last segment of its read structure.  Writes\n"
+    "                                              <OUTPUT>/trim-metrics.txt: per sample and read the reads scanned, trimmed for quality and for the\n"
+    "                                              adapter, the bases each cost, the reads held at the minimum length, the bases kept, and the reads\n"
+    "                                              over 512 bases, which are left alone.  --quality-metrics then reports the trimmed reads,\n"
+    "                                              --adapter-metrics the reads as they came in; not with --host-output (additive flag)\n"
+    "      --trim-quality <Q>                      cut low-quality 3' tails first (cutadapt's / BWA's algorithm, Phred cutoff Q from 1 to 93), with or\n"
+    "                                              without --trim-adapters (additive flag)\n"
+    "      --trim-rule <MINOVERLAP,ERRPCT>         the adapter rule of --trim-adapters [default: 5,10] (additive flag)\n"
+    "      --trim-min-length <N>                   a read is never cut below N bases, or below its own length if that is less [default: 1] (additive flag)\n"
     "      --index-pairs                           assign each of the two sample-barcode segments of the unmatched templates on its own\n"
     "                                              (--max-mismatches and --min-mismatch-delta per index) against the sample sheet's distinct\n"
     "                                              indexes, on the device, and write the pairs and their templates to <OUTPUT>/index-pairs.txt\n"
@@ -409,6 +427,18 @@ Options parse_args(int argc, char **argv) {
             if (!parse_adapter_rule(v, o.adapter_rule)) die("invalid value '" + v + "' for '--adapter-rule': expected MINOVERLAP,ERRPCT,SHORT (three non-negative integers)");
             o.adapter_rule_given = true;
         }
+        else if (a == "--trim-adapters") {
+            const std::string v = single();
+            o.trim_adapters.clear();
+            if (!parse_adapter_list(v, &o.trim_adapters)) die("invalid value '" + v + "' for '--trim-adapters': expected SEQ1[,SEQ2..] (adapter sequences, comma-separated)");
+        }
+        else if (a == "--trim-quality") num(&o.trim_quality);
+        else if (a == "--trim-rule") {
+            const std::string v = single();
+            if (!parse_trim_rule(v, o.trim_rule)) die("invalid value '" + v + "' for '--trim-rule': expected MINOVERLAP,ERRPCT (two non-negative integers)");
+            o.trim_rule_given = true;
+        }
+        else if (a == "--trim-min-length") { num(&o.trim_min_length); o.trim_min_length_given = true; }
         else if (a == "--help" || a == "-h") { std::fputs(kUsage, stdout); std::exit(0); }
         else die("unexpected argument '" + a + "' found\n\n" + kUsage);
     }
@@ -819,6 +849,23 @@ void write_adapter_metrics(const Options &opt, const std::vector<Sample> &sample
     if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
 }
 
+// --trim-adapters / --trim-quality: the table (summed over devices) as trim-metrics.txt
+void write_trim_metrics(const Options &opt, const std::vector<Sample> &samples, const TrimTable &table) {
+    std::vector<std::string> ids, barcodes;
+    for (const Sample &s : samples) { ids.push_back(s.sample_id); barcodes.push_back(s.barcode); }
+    ids.push_back(opt.unmatched_prefix);
+    barcodes.push_back(".");
+    const std::string path = opt.output + "/trim-metrics.txt", text = trim_tsv(table, ids, barcodes);
+    {
+        std::lock_guard<std::mutex> lk(g_created_mu);
+        g_created.push_back(path);
+    }
+    const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) die("cannot create " + path + ": " + std::strerror(errno));
+    write_all(fd, reinterpret_cast<const uint8_t *>(text.data()), text.size(), path);
+    if (::close(fd) != 0) die("write failed: " + path + ": " + std::strerror(errno));
+}
+
 [[noreturn]] void run_gpu_output(const Options &opt, const Plan &plan, const std::vector<Sample> &samples,
                                  std::vector<std::unique_ptr<FastqSource>> &sources, bool skip_few) {
     const size_t n_inputs = plan.rs.size(), S = samples.size(), G = opt.devices.size();
@@ -946,6 +993,13 @@ void write_adapter_metrics(const Options &opt, const std::vector<Sample> &sample
                 if (fqtk_demuxer_adapter_enable(demuxers[g], seqs.data(), (uint32_t)seqs.size(), (uint32_t)opt.adapter_rule[0], (uint32_t)opt.adapter_rule[1],
                                                 (uint32_t)opt.adapter_rule[2]) != FQTK_OK)
                     die(std::string("invalid use of '--adapter-metrics': ") + fqtk_last_error());
+            }
+            if (opt.trim()) {
+                std::vector<const char *> seqs;
+                for (const std::string &a : opt.trim_adapters) seqs.push_back(a.c_str());
+                if (fqtk_demuxer_trim_enable(demuxers[g], seqs.data(), (uint32_t)seqs.size(), (uint32_t)opt.trim_rule[0], (uint32_t)opt.trim_rule[1],
+                                             (uint32_t)std::min<unsigned long>(opt.trim_quality, 0xFFFFFFFFul), (uint32_t)std::min<unsigned long>(opt.trim_min_length, 0xFFFFFFFFul)) != FQTK_OK)
+                    die(std::string("invalid use of '--trim-adapters' / '--trim-quality': ") + fqtk_last_error());
             }
             if (opt.weighted && fqtk_demuxer_weighted_enable(demuxers[g], (uint32_t)opt.max_cost, (uint32_t)opt.min_cost_delta) != FQTK_OK)
                 die(std::string("cannot set up quality-weighted assignment: ") + fqtk_last_error());
@@ -1812,6 +1866,17 @@ void write_adapter_metrics(const Options &opt, const std::vector<Sample> &sample
                 if (at.row(s)[5 * j] + at.row(s)[5 * j + 4] != counts[s]) die("internal error: the adapter metrics' read counts differ from the per-sample counts");
         write_adapter_metrics(opt, samples, at);
     }
+    if (opt.trim()) {   // the devices' tables, summed (fqtk_demuxer_trim ADDS)
+        TrimTable tt;
+        tt.init(S, scanned_inputs(plan.rs));
+        if (tt.row_words != fqtk_demuxer_trim_row_words(demuxers[0])) die("internal error: the trim metrics' row differs from the read structures'");
+        for (size_t g = 0; g < G; ++g)
+            if (fqtk_demuxer_trim(demuxers[g], tt.v.data()) != FQTK_OK) die(fqtk_last_error());
+        for (size_t s = 0; s <= S; ++s)
+            for (size_t j = 0; j < tt.n_trimmed; ++j)
+                if (tt.row(s)[8 * j] + tt.row(s)[8 * j + 7] != counts[s]) die("internal error: the trim metrics' read counts differ from the per-sample counts");
+        write_trim_metrics(opt, samples, tt);
+    }
     if (!write_metrics_tsv(opt.output + "/demux-metrics.txt", rows, &err)) die(err);
     end_process();
 }
@@ -1956,6 +2021,13 @@ int main(int argc, char **argv) {
     if (!opt.adapters.empty() && (opt.host_output || env_on("FQTK_HOST_OUTPUT")))
         die("invalid use of '--adapter-metrics' with '--host-output': the host routers hold no text of the reads on the device; "
             "the adapter scan runs in the GPU record pipeline only");
+    if ((opt.trim_rule_given || opt.trim_min_length_given) && !opt.trim())
+        die(std::string("invalid use of '") + (opt.trim_rule_given ? "--trim-rule" : "--trim-min-length") +
+            "' without '--trim-adapters' or '--trim-quality': it is a parameter of that trimming and of nothing else");
+    if (opt.trim_rule_given && opt.trim_adapters.empty()) die("invalid use of '--trim-rule' without '--trim-adapters': it is the rule of the adapter cut and of nothing else");
+    if (opt.trim() && (opt.host_output || env_on("FQTK_HOST_OUTPUT")))
+        die(std::string("invalid use of '") + (opt.trim_adapters.empty() ? "--trim-quality" : "--trim-adapters") + "' with '--host-output': the host routers write the records "
+            "as they come in; trimming runs in the GPU record pipeline only");
     if (opt.weighted) {   // what the weighted rule does not take: said here, before any input is opened
         if (opt.host_output || env_on("FQTK_HOST_OUTPUT"))
             die("invalid use of '--quality-weighted' with '--host-output': the host routers carry no quality rows of the sample barcodes; "
@@ -2061,6 +2133,8 @@ int main(int argc, char **argv) {
             die("invalid use of '--per-index-mismatches': the GPU record pipeline does not take this configuration (" + why + "), and the host routers match whole barcodes");
         if (!opt.adapters.empty())
             die("invalid use of '--adapter-metrics': the GPU record pipeline does not take this configuration (" + why + "), and the host routers hold no text on the device");
+        if (opt.trim())
+            die("invalid use of '--trim-adapters' / '--trim-quality': the GPU record pipeline does not take this configuration (" + why + "), and the host routers do not trim");
         info("The GPU record pipeline does not take this configuration (%s): records are formatted and compressed on the host.", why.c_str());
     }
     const size_t G = opt.devices.size();

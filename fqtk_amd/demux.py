@@ -243,6 +243,20 @@ class Demuxer:
         _check(self._lib.fqtk_demuxer_adapter(self._h, a.ctypes.data))
         return a
 
+    def enable_trim(self, adapters: Sequence[str] = (), min_overlap: int = 5, max_error_pct: int = 10, quality_cutoff: int = 0, min_length: int = 1) -> None:
+        """3' quality and adapter trimming of every chunk's template reads on the device (before the first submit): the j-th input
+        that has a T segment is cut at its quality cut, then at adapters[min(j, len - 1)], never below min_length; the rule is stated
+        in include/fqtk_demux.h.  The files and quality() see the trimmed reads."""
+        arr = (C.c_char_p * max(len(adapters), 1))(*[a.encode() for a in adapters])
+        _check(self._lib.fqtk_demuxer_trim_enable(self._h, arr, len(adapters), int(min_overlap), int(max_error_pct), int(quality_cutoff), int(min_length)))
+
+    def trim(self) -> np.ndarray:
+        """[n_samples + 1, 8 * trimmed inputs] uint64: per trimmed input scanned, quality_trimmed, quality_bases, adapter_trimmed,
+        adapter_bases, floored, kept_bases, too_long (include/fqtk_demux.h); unmatched last."""
+        a = np.zeros((self.matcher.n_samples + 1, int(self._lib.fqtk_demuxer_trim_row_words(self._h))), dtype=np.uint64)
+        _check(self._lib.fqtk_demuxer_trim(self._h, a.ctypes.data))
+        return a
+
     def stage_seconds(self) -> Dict[str, float]:
         s = (C.c_double * _lib.FQTK_DEMUX_STAGES)()
         _check(self._lib.fqtk_demuxer_stage_seconds(self._h, s))

@@ -284,13 +284,44 @@ int fqtk_demuxer_quality(fqtk_demuxer *d, uint64_t *out);
  *   short_inserts += (p < short_insert).
  * A row is 5 counters per scanned input, in input order: [scanned, with_adapter, adapter_bases, short_inserts, too_long];
  * n_samples + 1 rows, unmatched last, kept across chunks.  scanned + too_long equals fqtk_demuxer_counts.  Exact integers.
- * Records are not changed: the scan only reports (csrc/adapter_kernels.hip.h).  Not enabled: no kernel runs, nothing is
+ * Records are not changed: the scan only reports (csrc/adapter_kernels.hip.h; fqtk_demuxer_trim_enable trims).  Not enabled: no kernel runs, nothing is
  * allocated; no scanned input: zero row words, no kernel either. */
 int fqtk_demuxer_adapter_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap,
                                 uint32_t max_error_pct, uint32_t short_insert);
 uint32_t fqtk_demuxer_adapter_row_words(const fqtk_demuxer *d);    /* 5 * scanned inputs */
 /* Adds the (n_samples + 1) rows of all collected chunks into out (so several devices sum); FQTK_EINVAL when not enabled. */
 int fqtk_demuxer_adapter(fqtk_demuxer *d, uint64_t *out);
+
+/* ---- 3' quality and adapter trimming of the template reads on the device (opt-in) -------------------------------------------------
+ * Parameters: adapters A_0 .. A_{k-1} under the constraints of fqtk_demuxer_adapter_enable, k = 0 allowed when quality_cutoff > 0;
+ * min_overlap and max_error_pct as there (read only when k > 0); quality_cutoff in 0..93, 0 = no quality trimming; min_length >= 1.
+ * A TRIMMED INPUT is an input whose read structure has a template (T) segment.  The j-th one uses adapter A_min(j, k-1); its span is
+ * the span of its last T segment, and that segment must be the LAST segment of the read structure (+T, 8B+T, 150T, 10T3M+T):
+ * shortening a record can only cut its tail, so 100T8B is FQTK_EINVAL and fqtk_last_error() names the input.  Also FQTK_EINVAL,
+ * naming the parameter: no trimmed input at all; nothing to do (k = 0 and quality_cutoff = 0); enabling after the first submit, or twice.
+ * For a template that is not dropped, s = its sample (unmatched -> n_samples), R[0..n) the span's sequence bytes, Q[0..n) its
+ * quality bytes, lo the span's start in the read:
+ *   n > 512: too_long += 1 for (s, input); the record is left as it is.  Otherwise scanned += 1, and
+ *   1. quality (cutadapt's / BWA's 3' algorithm on the raw Phred+33 bytes, unsigned):
+ *        s = 0; best = 0; n_q = n
+ *        for i = n-1 down to 0:  s += (quality_cutoff + 33) - Q[i];  if s < 0: stop;  if s > best: best = s, n_q = i
+ *      (quality_cutoff = 0: n_q = n)
+ *   2. adapter: the rule of fqtk_demuxer_adapter_enable on R[0..n_q) -- ov, mis(p), hit, smallest hit, with n_q in place of n.
+ *      cut = the smallest hit p, else n_q; k = 0: cut = n_q
+ *   3. floor: kept = max(cut, min(min_length, n)) -- a written read never has fewer bases than min_length or than it came with,
+ *      and is never empty
+ *   4. the record's sequence and quality are written as their first lo + kept bytes.
+ * A row is 8 counters per trimmed input, in input order: [scanned, quality_trimmed (n_q < n), quality_bases (n - n_q),
+ * adapter_trimmed (cut < n_q), adapter_bases (n_q - cut), floored (kept > cut), kept_bases (kept), too_long]; n_samples + 1 rows,
+ * unmatched last, kept across chunks.  scanned + too_long equals fqtk_demuxer_counts.  Exact integers.
+ * The step runs behind the matcher and in front of placement (csrc/trim_kernels.hip.h): the files, the quality tally
+ * (fqtk_demuxer_quality) and everything else behind it see the trimmed records; the adapter metrics (fqtk_demuxer_adapter), when
+ * enabled too, report on the reads as they came in.  Not enabled: no kernel runs, nothing is allocated, every output byte is the same. */
+int fqtk_demuxer_trim_enable(fqtk_demuxer *d, const char *const *adapters, uint32_t n_adapters, uint32_t min_overlap,
+                             uint32_t max_error_pct, uint32_t quality_cutoff, uint32_t min_length);
+uint32_t fqtk_demuxer_trim_row_words(const fqtk_demuxer *d);       /* 8 * trimmed inputs */
+/* Adds the (n_samples + 1) rows of all collected chunks into out (so several devices sum); FQTK_EINVAL when not enabled. */
+int fqtk_demuxer_trim(fqtk_demuxer *d, uint64_t *out);
 
 /* Seconds of device time per stage, summed over the chunks collected so far (names: fqtk_demuxer_stage_name). */
 #define FQTK_DEMUX_STAGES 8
